@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """Headline benchmark: upscaled megapixels/s of the FSR 1.0 hot path (EASU + RCAS) on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+  A plain run does what the headline figure needs and nothing else: set-up, the clock ramp, W warm-up steps, K timed steps (one region),
+  the result line.  --dump-outputs DIR also writes the image the last timed step produced (DIR/output.npy, float32; a fixed seeded
+  sample of its pixels where the whole image is too large), so that two builds can be compared output for output.  --full adds
+  everything else this file measures or checks (R = 7 timed regions and their median, the one-stream step, steady-state windows,
+  per-kernel stopwatch and roofline, the other pipelines / arithmetics / presets, latency, telemetry, the host's submission ceiling,
+  the CPU baseline and the image-level parity block).
   N > 1, either launch style gives the same run and ONE JSON line:
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
     python bench.py --gpus N ...      (no WORLD_SIZE in the environment: bench.py starts the N ranks itself, the same way)
@@ -103,7 +109,7 @@ class Telemetry:
     (/sys/bus/pci/devices/<domain:bus:dev.fn>/hwmon/hwmon*/): freq1_input (sclk, Hz), power1_average or power1_input (uW).
     Everything is best effort: a file that is missing or unreadable leaves that figure null; the run is never failed by it."""
 
-    def __init__(self, torch, dev_index, period=0.002):
+    def __init__(self, torch, dev_index, period=0.002, sample=True):
         import glob
         import threading
         self.period = period
@@ -159,7 +165,7 @@ class Telemetry:
                         pass
         except Exception:
             pass
-        if self.freq or self.power:
+        if sample and (self.freq or self.power):  # (sample=False: only the static facts above, which the CPU pinning needs)
             self._thread = threading.Thread(target=self._run, daemon=True)
             self._thread.start()
 
@@ -538,13 +544,39 @@ def cpu_baseline(fsr, in_w, in_h, out_w, out_h, target_seconds=12.0, keep=None):
     }
 
 
+DUMP_MAX_BYTES = 32 << 20  # of float32 per dumped array (one 4K RGBA image is 133 MB as float32)
+DUMP_SEED = 20210622
+
+
+def dump_output(directory, name, image):
+    """--dump-outputs: `image` (a device tensor, [..., channels]) as directory/name.npy in float32 — every pixel when that fits
+    DUMP_MAX_BYTES, else a sample of pixels whose indices depend on the image's shape and DUMP_SEED only (drawn with replacement and
+    sorted, picked on the device so that only the sample crosses PCIe): the same arguments give the same pixels in every run and build."""
+    import numpy as np
+    import torch
+    px = image.reshape(-1, image.shape[-1])
+    keep = DUMP_MAX_BYTES // (4 * px.shape[1])
+    if px.shape[0] > keep:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, px.shape[0], size=keep))
+        px = px[torch.from_numpy(idx).to(px.device)]
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, name + ".npy"), px.cpu().numpy().astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=200)
-    ap.add_argument("--regions", type=int, default=7,
-                    help="timed regions of exactly --steps steps each (barrier + synchronize either side); the line reports the median region")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline, run everything else this file measures or checks (see the module docstring); a plain run without it "
+                         "only sets up, warms up, times --steps steps and prints the line with the headline's fields")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the image their last step produced as DIR/output.npy (float32; output_rankR.npy per rank at "
+                         "--gpus N > 1); a fixed seeded sample of its pixels where the whole image exceeds %d MB" % (DUMP_MAX_BYTES >> 20))
+    ap.add_argument("--regions", type=int, default=None,
+                    help="timed regions of exactly --steps steps each (barrier + synchronize either side); the line reports the median region. "
+                         "Default 1: --steps is the number of timed steps; 7 with --full (and in the --stub fixture)")
     ap.add_argument("--streams", type=int, default=3,
                     help="HIP streams per GPU the steps alternate over (fsr1_pipeline: step i on stream i mod S, each stream with its own "
                          "intermediary, so the tail of one step overlaps the head of the next); 1 = every step on one in-order stream, "
@@ -602,6 +634,8 @@ def main():
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.regions is None:
+        args.regions = 7 if (args.full or args.stub) else 1
     if args.regions < 1:
         raise SystemExit("--regions must be >= 1")
     if not 1 <= args.streams <= 8:
@@ -646,7 +680,8 @@ def main():
             dist.init_process_group("gloo")
     coll_device = device if args.backend == "nccl" else torch.device("cpu")
 
-    tele = Telemetry(torch, dev_index)  # (the sampling thread runs from here on; figures are taken from labelled spans only)
+    # (--full: the sampling thread runs from here on; figures are taken from labelled spans only.  A plain run reads the device's NUMA facts alone)
+    tele = Telemetry(torch, dev_index, sample=args.full)
     cpu_binding = bind_to_gpu_cpus(tele, enabled=not args.no_pin)
     cpu_binding_before = cpu_binding.pop("_before", None) or os.sched_getaffinity(0)
     if args.submit_only:
@@ -714,8 +749,9 @@ def main():
     if args.pipeline == "color":
         if not stages:
             raise SystemExit("--pipeline color needs --stages")
-        srcs = [torch.rand(frames, out_h, out_w, 4, device=device).to(tdtype) if tdtype != torch.uint8 else
-                torch.randint(0, 256, (frames, out_h, out_w, 4), device=device, dtype=torch.uint8) for _ in range(ring)]
+        gd = torch.Generator(device=device).manual_seed(1234 + rank)  # (seeded: the same arguments give the same inputs in every run)
+        srcs = [torch.rand(frames, out_h, out_w, 4, device=device, generator=gd).to(tdtype) if tdtype != torch.uint8 else
+                torch.randint(0, 256, (frames, out_h, out_w, 4), device=device, dtype=torch.uint8, generator=gd) for _ in range(ring)]
     easu_con = fsr.FsrEasuCon(in_w, in_h, in_w, in_h, out_w, out_h)
     rcas_con = fsr.FsrRcasCon(0.25)  # sample default attenuation (SampleRenderer.h:49)
 
@@ -777,7 +813,8 @@ def main():
     # Device clock ramp (not part of W): an idle MI355X sits at ~100 MHz and needs a few milliseconds of load
     # to reach its working clocks; EASU then runs AT the 1400 W package power cap (sclk ~2.1 of 2.4 GHz), so the
     # steady state is what a frame stream sees.  ~0.2 s of the same steps, untimed.
-    viol0 = tele.violations(dev_index) if not args.no_telemetry_window else None  # (before the ramp: the GPU is idle anyway)
+    window = args.full and not args.no_telemetry_window
+    viol0 = tele.violations(dev_index) if window else None  # (before the ramp: the GPU is idle anyway)
     t_ramp = time.perf_counter()
     i = 0
     while time.perf_counter() - t_ramp < 0.2:
@@ -789,7 +826,7 @@ def main():
     # Telemetry window (not part of W, outside every timed region): TELEMETRY_WINDOW_S of the headline's own pipelined load, sampled every 2 ms —
     # 500+ samples whatever --steps is (round 5 sampled across the run itself: at the driver's K = 20 that was 57 samples of a 0.1 s load and
     # read 20 % low).  The SMU's throttle accumulators are read before and after it: their difference says which limiter was active.
-    if not args.no_telemetry_window:
+    if window:
         tele.begin("headline")
         t_win = time.perf_counter()
         while time.perf_counter() - t_win < TELEMETRY_WINDOW_S:
@@ -842,9 +879,14 @@ def main():
                     pipe.join(cap)
         g.replay()
         regions, own_regions = timed(lambda i: g.replay(), args.steps // args.graph)
+        last_step = args.graph - 1
     else:
         regions, own_regions = timed(step, args.steps, first=args.warmup)
+        last_step = args.warmup + args.regions * args.steps - 1
     seconds = median(regions)
+    if args.dump_outputs:
+        # what the last timed step handed its caller: the output image of its ring slot (taken now: with --full, later sections write the ring again)
+        dump_output(args.dump_outputs, "output" if world == 1 else "output_rank%d" % rank, dsts[last_step % ring])
 
     def steady(fn, k, stream_of_last):
         """Steady state: R windows of exactly k steps timed INSIDE one longer run — `lead` steps in front (the pipeline fills), R x k
@@ -876,8 +918,70 @@ def main():
         return pipe._slot_stream((pipe.next_slot() - 1) % pipe.streams)
 
     steady_regions = None
-    if not args.no_steady and args.graph == 0:
+    if args.full and not args.no_steady and args.graph == 0:
         steady_regions = steady(step, args.steps, last_pipe_stream if pipe is not None else (lambda: None))
+
+    total = reduce_counters(frames * args.steps, frames * args.steps * out_w * out_h, median(own_regions), coll_device)
+    total["seconds"] = seconds  # median over regions of the max over ranks
+    per_rank_seconds = gather_seconds(median(own_regions), coll_device)
+    value = total["pixels"] / total["seconds"] / 1e6
+
+    # the headline's fields: all a plain run prints (--full adds its sections to this line further down)
+    line = {
+        "metric": {"easu": "upscaled megapixels/sec (EASU only)", "color": "megapixels/sec (colour pass)"}.get(
+            args.pipeline, "upscaled megapixels/sec (EASU+RCAS, %s %s)" % ("1080p->4K" if args.workload == "1080p_to_4k" else args.workload,
+                                                                              {"rgba16f": "fp16", "rgba8": "rgba8 unorm", "rgba32f": "fp32 storage"}[args.storage])),
+        "value": round(value, 1), "unit": "Mpix/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(total["seconds"] * 1e3 / args.steps, 5), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": (round(value / world / {(3840, 2160): PUBLISHED_4K_MPIX_S, (2560, 1440): PUBLISHED_1440P_MPIX_S}[(out_w, out_h)], 2)
+                        if (out_w, out_h) in ((3840, 2160), (2560, 1440)) and args.pipeline in ("two-pass", "fused") and not args.stages else None),
+        "vs_baseline_ref": "per GPU, vs BASELINE.md §1: EASU+RCAS <= 0.40 ms per 4K frame (<= 0.20 ms per 1440p frame) on RX 6800 XT / RTX 3080 (reference PDF p.9) = >= 20736 (18432) Mpix/s; "
+                           "an upper bound on time, measured on other hardware",
+        "dtype": "f32" if args.math != "h" else "f16", "data": "synthetic",
+        # which parity class the headline's arithmetic belongs to (include/fsr1_hip.h, FSR1_FLAG_MATH_*):
+        #   F-default: fp32 arithmetic, per stage <= 1 binary16 ULP of the CPU-evaluated FsrEasuF / FsrRcasF; image level: see `parity`
+        #   EXACT: bit-identical to the reference chain;  H: bit-identical to the CPU-evaluated FsrEasuH / FsrRcasH
+        #   F-strict (round 6): fp32 arithmetic, EASU's stored image bit-identical to FsrEasuF's, the final image within 1 binary16 ULP of the chain
+        "parity_class": {"strict": "F-strict", "f": "F-default", "exact": "EXACT", "h": "H"}[args.math],
+        "full": bool(args.full),
+        "config": {"workload": "%s: %dx%d -> %dx%d %s, %d frame(s)/step/GPU, %s, math=%s, ring of %d frame sets"
+                               % (args.workload, in_w, in_h, out_w, out_h, args.storage.upper(), frames, args.pipeline, args.math, ring)
+                               + (" (inputs / outputs; one reused intermediary)" if args.pipeline == "two-pass" else ""),
+                   "source_hash": fsr._lib.source_hash(), "build_id": fsr._lib.build_id(),
+                   "binary_matches_sources": fsr._lib.build_id() == fsr._lib.source_hash(),
+                   "intermediary": None if args.pipeline != "two-pass" else ("one per stream" if pipe is not None else ("rotated" if args.rotate_intermediary else "reused")),
+                   "launch": launch_style(), "world_size_seen": dist.get_world_size() if grouped else 1,
+                   "cpu_binding": cpu_binding,
+                   "collective_backend": (("rccl (torch.distributed 'nccl')" if args.backend == "nccl" else "gloo") if grouped else None),
+                   "devices_visible": n_dev, "oversubscribed": bool(world > n_dev),
+                   "streams": args.streams,
+                   "pipelining": ("step i runs on HIP stream i mod %d (fsr1_pipeline), each stream with its own EASU->RCAS intermediary: frames are independent, so the "
+                                  "tail of one step overlaps the head of the next (a kernel boundary costs ~5 us of an otherwise idle chip)" % args.streams)
+                                 if pipe is not None else "none: one in-order stream",
+                   "regions": args.regions,
+                   "region_ms_per_step": {"median": round(median(regions) * 1e3 / args.steps, 5), "min": round(min(regions) * 1e3 / args.steps, 5),
+                                          "max": round(max(regions) * 1e3 / args.steps, 5)},
+                   "timing": "R = `regions` timed regions of exactly K = `steps` steps, each bracketed by barrier + synchronize on both sides and "
+                             "reduced with MAX over ranks; value / ms_per_step are the MEDIAN region (a K = 20 region of 4K frames is 1.3 ms: the first "
+                             "launch's latency and the closing synchronize are 1-6 % of it, so single regions scatter by that much)",
+                   "pipeline": args.pipeline, "storage": args.storage, "color_stages": args.stages, "hip_graph_steps": args.graph, "rcas_sharpness_stops": 0.25,
+                   "parallelism": "independent frames per GPU, counters-only collective"},
+        # the headline `value` is the pipelined figure (`streams` HIP streams per GPU, the product's way to run a frame stream)
+        "streams": args.streams,
+        "per_rank_seconds": [round(t, 6) for t in per_rank_seconds],
+    }
+
+    def finish():
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if pipe is not None:
+            pipe.close()
+        if grouped:
+            dist.destroy_process_group()
+
+    if not args.full:
+        tele.close()
+        return finish()
 
     # the same K steps on ONE in-order stream (the method of rounds 1-3): the per-kernel stopwatch below is taken that way, and the
     # line's self-consistency check compares the kernels with THIS step (overlapped steps are shorter than the kernels they contain)
@@ -885,11 +989,6 @@ def main():
     one_regions = timed(step1, args.steps, first=args.warmup)[0] if pipe is not None else regions
     one_steady = steady(step1, args.steps, lambda: None) if (pipe is not None and steady_regions is not None) else steady_regions
     tele.end("one_stream")
-
-    total = reduce_counters(frames * args.steps, frames * args.steps * out_w * out_h, median(own_regions), coll_device)
-    total["seconds"] = seconds  # median over regions of the max over ranks
-    per_rank_seconds = gather_seconds(median(own_regions), coll_device)
-    value = total["pixels"] / total["seconds"] / 1e6
 
     # ---- per-kernel durations with HIP events on the launch stream (C-ABI stopwatch) ----
     # Taken right after the headline regions (same clocks, same buffers) and INDEPENDENT of --steps: after a ramp of the very
@@ -1146,51 +1245,11 @@ def main():
         return r
 
     if rank == 0:
-        line = {
-            "metric": {"easu": "upscaled megapixels/sec (EASU only)", "color": "megapixels/sec (colour pass)"}.get(
-                args.pipeline, "upscaled megapixels/sec (EASU+RCAS, %s %s)" % ("1080p->4K" if args.workload == "1080p_to_4k" else args.workload,
-                                                                                  {"rgba16f": "fp16", "rgba8": "rgba8 unorm", "rgba32f": "fp32 storage"}[args.storage])),
-            "value": round(value, 1), "unit": "Mpix/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(total["seconds"] * 1e3 / args.steps, 5), "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": (round(value / world / {(3840, 2160): PUBLISHED_4K_MPIX_S, (2560, 1440): PUBLISHED_1440P_MPIX_S}[(out_w, out_h)], 2)
-                            if (out_w, out_h) in ((3840, 2160), (2560, 1440)) and args.pipeline in ("two-pass", "fused") and not args.stages else None),
-            "vs_baseline_ref": "per GPU, vs BASELINE.md §1: EASU+RCAS <= 0.40 ms per 4K frame (<= 0.20 ms per 1440p frame) on RX 6800 XT / RTX 3080 (reference PDF p.9) = >= 20736 (18432) Mpix/s; "
-                               "an upper bound on time, measured on other hardware",
-            "dtype": "f32" if args.math != "h" else "f16", "data": "synthetic",
-            # which parity class the headline's arithmetic belongs to (include/fsr1_hip.h, FSR1_FLAG_MATH_*):
-            #   F-default: fp32 arithmetic, per stage <= 1 binary16 ULP of the CPU-evaluated FsrEasuF / FsrRcasF; image level: see `parity`
-            #   EXACT: bit-identical to the reference chain;  H: bit-identical to the CPU-evaluated FsrEasuH / FsrRcasH
-            #   F-strict (round 6): fp32 arithmetic, EASU's stored image bit-identical to FsrEasuF's, the final image within 1 binary16 ULP of the chain
-            "parity_class": {"strict": "F-strict", "f": "F-default", "exact": "EXACT", "h": "H"}[args.math],
-            "config": {"workload": "%s: %dx%d -> %dx%d %s, %d frame(s)/step/GPU, %s, math=%s, ring of %d frame sets"
-                                   % (args.workload, in_w, in_h, out_w, out_h, args.storage.upper(), frames, args.pipeline, args.math, ring)
-                                   + (" (inputs / outputs; one reused intermediary)" if args.pipeline == "two-pass" else ""),
-                       "source_hash": fsr._lib.source_hash(), "build_id": fsr._lib.build_id(),
-                       "binary_matches_sources": fsr._lib.build_id() == fsr._lib.source_hash(),
-                       "intermediary": None if args.pipeline != "two-pass" else ("one per stream" if pipe is not None else ("rotated" if args.rotate_intermediary else "reused")),
-                       "launch": launch_style(), "world_size_seen": dist.get_world_size() if grouped else 1,
-                       "cpu_binding": cpu_binding,
-                       "collective_backend": (("rccl (torch.distributed 'nccl')" if args.backend == "nccl" else "gloo") if grouped else None),
-                       "devices_visible": n_dev, "oversubscribed": bool(world > n_dev),
-                       "streams": args.streams,
-                       "one_stream": {"value": round(total["pixels"] / median(one_regions) / 1e6, 1), "ms_per_step": round(median(one_regions) * 1e3 / args.steps, 5),
-                                      "note": "the same K steps on one in-order HIP stream (the method of rounds 1-3; what the kernels' durations add up to)"},
-                       "pipelining": ("step i runs on HIP stream i mod %d (fsr1_pipeline), each stream with its own EASU->RCAS intermediary: frames are independent, so the "
-                                      "tail of one step overlaps the head of the next (a kernel boundary costs ~5 us of an otherwise idle chip)" % args.streams)
-                                     if pipe is not None else "none: one in-order stream",
-                       "regions": args.regions,
-                       "region_ms_per_step": {"median": round(median(regions) * 1e3 / args.steps, 5), "min": round(min(regions) * 1e3 / args.steps, 5),
-                                              "max": round(max(regions) * 1e3 / args.steps, 5)},
-                       "timing": "R = `regions` timed regions of exactly K = `steps` steps, each bracketed by barrier + synchronize on both sides and "
-                                 "reduced with MAX over ranks; value / ms_per_step are the MEDIAN region (a K = 20 region of 4K frames is 1.3 ms: the first "
-                                 "launch's latency and the closing synchronize are 1-6 % of it, so single regions scatter by that much)",
-                       "pipeline": args.pipeline, "storage": args.storage, "color_stages": args.stages, "hip_graph_steps": args.graph, "rcas_sharpness_stops": 0.25,
-                       "parallelism": "independent frames per GPU, counters-only collective"},
-            # the headline `value` is the pipelined figure (`streams` HIP streams per GPU, the product's way to run a frame stream); the same K
-            # steps on ONE in-order stream — the method of rounds 1-3, and what the kernels' durations add up to — at the top level beside it
-            "streams": args.streams,
-            "one_stream": {"value": round(total["pixels"] / median(one_regions) / 1e6, 1), "ms_per_step": round(median(one_regions) * 1e3 / args.steps, 5)},
-            "per_rank_seconds": [round(t, 6) for t in per_rank_seconds],
+        one = {"value": round(total["pixels"] / median(one_regions) / 1e6, 1), "ms_per_step": round(median(one_regions) * 1e3 / args.steps, 5)}
+        line["config"]["one_stream"] = dict(one, note="the same K steps on one in-order HIP stream (the method of rounds 1-3; what the kernels' durations add up to)")
+        line.update({
+            # beside the pipelined headline: the same K steps on ONE in-order stream — the method of rounds 1-3, and what the kernels' durations add up to
+            "one_stream": one,
             # shader clock (median MHz) and package power (mean W) every rank's GPU showed under the headline's load — a dedicated window of
             # TELEMETRY_WINDOW_S of it before the timed regions (`telemetry.window`) — read from the amdgpu driver's sysfs files by a host
             # thread; null where a box does not expose them
@@ -1207,7 +1266,7 @@ def main():
             "kernels": {k: roof(k) for k in kern},
             "pipeline_hbm": {"algorithmic_bytes_per_step": sum(alg[k] for k in kern),
                              "achieved_GBps": round(sum(alg[k] for k in kern) * args.steps / seconds / 1e9, 1)},
-        }
+        })
         if steady_regions is not None:
             def _st(reg):
                 return {"value": round(total["pixels"] / median(reg) / 1e6, 1), "ms_per_step": round(median(reg) * 1e3 / args.steps, 5),
@@ -1272,11 +1331,7 @@ def main():
                     fsr.rcas(p_mid, p_out["two_dispatch"], con=rcas_con, flags=fl)
                     h = image_parity.ulp_histogram(p_out["two_dispatch"], kept["want"])
                     line["parity"][{"exact": "exact_arithmetic", "strict": "strict_arithmetic", "f": "default_arithmetic"}[other] + "_two_dispatch"] = {kk: h[kk] for kk in keys}
-        print(json.dumps(line), flush=True)
-    if pipe is not None:
-        pipe.close()
-    if grouped:
-        dist.destroy_process_group()
+    finish()
 
 
 if __name__ == "__main__":

@@ -6,6 +6,8 @@ import copy
 import os
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
@@ -110,3 +112,55 @@ def test_telemetry_block_marks_a_short_sample_unreliable():
     none = bench.telemetry_block([[None, None, None, None, None, None]], None, 2.0, bench.TELEMETRY_WINDOW_S, None)
     assert none["reliable"] is False and none["at_power_cap"] == [None]
     assert bench.TELEMETRY_WINDOW_S / 0.002 >= 2 * bench.TELEMETRY_MIN_SAMPLES  # the window is sized for twice the minimum
+
+
+def test_dump_output_whole_image_and_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: an image within the budget is written whole, as float32; a larger one as a sample of its pixels that depends on the
+    image's shape and the fixed seed only — the same pixels in every run, in image order, never more than the budget."""
+    import numpy as np
+    import torch
+    img = torch.arange(2 * 6 * 5 * 4, dtype=torch.float16).reshape(2, 6, 5, 4)
+    bench.dump_output(str(tmp_path / "a"), "output", img)
+    whole = np.load(tmp_path / "a" / "output.npy")
+    assert whole.dtype == np.float32 and whole.shape == (60, 4) and np.array_equal(whole, img.reshape(60, 4).float().numpy())
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 16 * 4 * 4)  # room for 16 pixels of 4 float32 channels
+    bench.dump_output(str(tmp_path / "a"), "sample", img)
+    bench.dump_output(str(tmp_path / "b"), "sample", img + 0)
+    s1, s2 = np.load(tmp_path / "a" / "sample.npy"), np.load(tmp_path / "b" / "sample.npy")
+    assert s1.dtype == np.float32 and s1.shape == (16, 4) and s1.nbytes <= bench.DUMP_MAX_BYTES and np.array_equal(s1, s2)
+    pixel = (s1[:, 0] / 4).astype(np.int64)  # (pixel p of this image holds 4p .. 4p + 3)
+    assert np.array_equal(s1, whole[pixel]) and np.all(np.diff(pixel) >= 0) and len(set(pixel.tolist())) > 4
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_once_and_dumps_its_last_output(tmp_path, fsr):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` is the headline alone: one timed region of exactly K steps and none of the sections that
+    moved behind --full; --dump-outputs writes the image the last timed step produced — here small enough to be written whole, and equal
+    to what the library gives for that step's ring slot when called directly."""
+    import json
+    import subprocess
+    import numpy as np
+    import torch
+    K, W = 7, 3
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(K), "--warmup", str(W), "--workload", "270p_to_540p",
+                          "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert line["steps"] == K and line["warmup"] == W and line["config"]["regions"] == 1 and line["full"] is False
+    assert line["value"] > 0 and line["ms_per_step"] > 0 and line["unit"] == "Mpix/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+    assert abs(line["value"] - 960 * 540 / (line["ms_per_step"] * 1e-3) / 1e6) <= 1e-3 * line["value"]
+    for moved in ("roofline", "kernels", "also_measured", "latency_us", "cpu_baseline", "parity", "steady_state", "telemetry", "host_submission", "one_stream"):
+        assert moved not in line, moved
+    got = np.load(tmp_path / "output.npy")
+    assert got.dtype == np.float32 and got.shape == (960 * 540, 4)
+    ring = int(line["config"]["workload"].split("ring of ")[1].split()[0])
+    s = (W + K - 1) % ring  # the last timed step's ring slot; its input is frame 0 rolled by (3 s, 5 s)
+    src = torch.roll(torch.from_numpy(fsr.frames.synthetic_frame(480, 270, k=0)).cuda(), shifts=(3 * s, 5 * s), dims=(0, 1)).contiguous().unsqueeze(0)
+    mid = torch.empty(1, 540, 960, 4, dtype=torch.float16, device="cuda")
+    dst = torch.empty_like(mid)
+    fsr.easu(src, mid, con=fsr.FsrEasuCon(480, 270, 480, 270, 960, 540), flags=fsr.FLAG_MATH_STRICT)
+    fsr.rcas(mid, dst, con=fsr.FsrRcasCon(0.25), flags=fsr.FLAG_MATH_STRICT)
+    torch.cuda.synchronize()
+    assert np.array_equal(got, dst.reshape(-1, 4).float().cpu().numpy())

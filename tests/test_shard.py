@@ -104,7 +104,7 @@ def test_bench_self_launch_two_ranks_on_the_visible_gpus():
     RCCL when two GPUs are visible, over gloo with the ranks sharing the one GPU otherwise (RCCL refuses two ranks on a device)."""
     torch = pytest.importorskip("torch")
     two = torch.cuda.device_count() >= 2
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "30", "--warmup", "5", "--no-cpu-baseline", "--workload", "540p_to_1080p"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "30", "--warmup", "5", "--full", "--no-cpu-baseline", "--workload", "540p_to_1080p"]
     if not two:
         cmd += ["--backend", "gloo", "--oversubscribe"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "FSR1_BENCH_SELF_LAUNCHED")}

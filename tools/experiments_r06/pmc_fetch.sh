@@ -4,7 +4,7 @@
 TAG=$1; LIB=$2; shift; shift
 ROOT=$PWD; RAW=/tmp/pmc_$TAG; rm -rf $RAW; mkdir -p $RAW; export TMPDIR=/tmp
 [ -n "$LIB" ] && export FSR1_HIP_LIB=$ROOT/$LIB
-BENCH="python $ROOT/bench.py --no-cpu-baseline --no-cold-rcas --no-also --no-latency --no-steady --no-parity --no-telemetry-window --no-submit-ceiling --streams 1 $*"
+BENCH="python $ROOT/bench.py --full --no-cpu-baseline --no-cold-rcas --no-also --no-latency --no-steady --no-parity --no-telemetry-window --no-submit-ceiling --streams 1 $*"
 cd /tmp
 for pass in "fetch:FETCH_SIZE" "write:WRITE_SIZE" "tcc:TCC_HIT_sum TCC_MISS_sum"; do
   name=${pass%%:*}; ctrs=${pass#*:}
