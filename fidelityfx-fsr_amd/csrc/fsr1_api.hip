@@ -23,24 +23,25 @@ void rcas_geometry(int width, int height, int frames, bool overlapped, int* tile
 hipError_t fused_launch(const FusedArgs& a, int fmt, bool exact, hipStream_t stream, bool strict);
 size_t fused_strict_lds_bytes(int fmt, int fp_w, int fp_h);
 size_t fused_lds_bytes(int fmt, int fp_w, int fp_h);
-hipError_t fused_h_launch(const FusedArgs& a, hipStream_t stream);
+hipError_t fused_h_launch(const FusedArgs& a, int fmt, hipStream_t stream);
 hipError_t fused_s2_launch(const FusedArgs& a, int fmt, bool exact, bool tall, hipStream_t stream, bool strict);
 size_t fused_s2_lds_bytes(int fmt, int waves);
 size_t fused_s2_strict_lds_bytes(int fmt, int waves);
 bool fused_s2_tall_tiles(int width, int height, int frames, int steps, int cus, int fmt);
 void fused_s2_geometry(int width, int height, int steps, int* tiles_x, int* tiles_y, int step_rows);
 int fused_s2_run_steps(int width, int height, int frames, int cus, int wgs_per_cu, bool overlapped, bool strict);
-hipError_t fused_s2_h_launch(const FusedArgs& a, hipStream_t stream);
+hipError_t fused_s2_h_launch(const FusedArgs& a, int fmt, hipStream_t stream);
 size_t fused_s2_h_lds_bytes();
 size_t fused_h_lds_bytes(int fp_w, int fp_h);
-hipError_t easu_h_launch(const EasuArgs& a, bool s2, hipStream_t stream);
+hipError_t easu_h_launch(const EasuArgs& a, int fmt, bool s2, hipStream_t stream);
 hipError_t easu_color_launch(const EasuArgs& a, int fin, int fout, bool exact, hipStream_t stream);
 hipError_t rcas_color_launch(const RcasArgs& a, int fin, int fout, bool exact, hipStream_t stream);
 hipError_t fused_color_launch(const FusedArgs& a, int fin, int fout, bool exact, hipStream_t stream);
 hipError_t color_launch(const ColorPassArgs& a, int fin, int fout, bool exact, hipStream_t stream);
 hipError_t color_h_launch(const ColorPassArgs& a, hipStream_t stream);
 void color_geometry(int width, int height, int* tiles_x, int* tiles_y);
-hipError_t rcas_h_launch(const RcasArgs& a, hipStream_t stream);
+hipError_t rcas_h_launch(const RcasArgs& a, int fmt, hipStream_t stream);
+void rcas_h_geometry(int fmt, int width, int height, int* tiles_x, int* tiles_y);
 }  // namespace fsr1
 
 using namespace fsr1;
@@ -116,6 +117,12 @@ static int fail(int code, const char* fmt, ...) {
 }
 static int hip_fail(hipError_t e, const char* what) {
   return fail(FSR1_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
+}
+
+// Packed-fp16 (class H) kernels exist for RGBA16F and for the two 32 bpp UNORM formats (the reference's shipping combination:
+// FsrEasuH / FsrRcasH over R8G8B8A8_UNORM / R10G10B10A2_UNORM images); RGBA32F storage has no H kernels.
+static bool packed_format_ok(int fmt) {
+  return fmt == FSR1_FORMAT_RGBA16F || fmt == FSR1_FORMAT_RGBA8_UNORM || fmt == FSR1_FORMAT_R10G10B10A2_UNORM;
 }
 
 static size_t pixel_bytes(int fmt) { return fmt == FSR1_FORMAT_RGBA32F ? 16 : (fmt == FSR1_FORMAT_RGBA16F ? 8 : 4); }
@@ -318,6 +325,7 @@ static bool auto_takes_fused(const fsr1_image* in, bool have_intermediary, const
   // launch, two dispatches / fused): 540p -> 1080p 34.8 / 29.8, 720p -> 1440p 50.9 / 47.0, one 4K frame 93.7 / 95.6, four 4K frames or
   // one 8K frame 348 / 359, eight 4K frames 708 / 685, four 8K frames 1347 / 1345, eight 2690 / 2640, sixteen 5450 / 5240: the fused
   // launch up to 4 Mpixel of output and from 60 Mpixel up, the two dispatches between.
+  // (measured on RGBA16F storage; the 32 bpp UNORM formats reuse the thresholds unmeasured)
   const bool packed_2x = con_2x && packed && !(math & FSR1_FLAG_NO_FAST_PATHS) && !have_stages;
   if (packed_2x && (out_pixels <= 4000000ll || out_pixels >= 60000000ll)) return true;
   return quad_form || out_pixels <= 3000000ll;
@@ -389,6 +397,8 @@ static int easu_dispatch_impl(const fsr1_image* in, const fsr1_image* out, const
   a.fp_w = footprint_extent(out->width, kTileW, 0, sx, bx, origin_x);
   a.fp_h = footprint_extent(out->height, kTileH, 0, sy, by, origin_y);
   if (a.fp_w < 0 || a.fp_h < 0) return fail(FSR1_ERR_INVALID_ARGUMENT, "easu: scale constants con0.xy = (%g, %g) are not usable", sx, sy);
+  // (the H kernels' LDS records are binary16 whatever the storage format, so no LDS budget of class H depends on the format: the bound
+  //  below, fused_h_lds_bytes and fused_s2_h_lds_bytes hold for RGBA16F and the 32 bpp UNORM formats alike)
   if (easu_lds_bytes(in->format, a.fp_w, a.fp_h) > device_lds_per_cu())
     return fail(FSR1_ERR_UNSUPPORTED, "easu: input/output ratio (%g, %g) needs a %dx%d texel footprint per tile, beyond the LDS budget "
                                       "(EASU is an upscaler; ratios up to ~3x minification are supported)", sx, sy, a.fp_w, a.fp_h);
@@ -437,8 +447,8 @@ static int easu_dispatch_impl(const fsr1_image* in, const fsr1_image* out, const
   if ((rc = check_grid("easu", a.tiles_x, a.tiles_y, a.frames))) return rc;
   hipError_t e;
   if (flags & FSR1_FLAG_MATH_PACKED_FP16) {
-    if (in->format != FSR1_FORMAT_RGBA16F) return fail(FSR1_ERR_UNSUPPORTED, "easu: packed-fp16 math needs RGBA16F images");
-    e = easu_h_launch(a, s2, static_cast<hipStream_t>(stream));
+    if (!packed_format_ok(in->format)) return fail(FSR1_ERR_UNSUPPORTED, "easu: packed-fp16 math needs RGBA16F, RGBA8_UNORM or R10G10B10A2_UNORM images");
+    e = easu_h_launch(a, in->format, s2, static_cast<hipStream_t>(stream));
   } else if (a.color.stages) {
     e = easu_color_launch(a, in->format, out->format, (flags & FSR1_FLAG_MATH_EXACT) != 0, static_cast<hipStream_t>(stream));
   } else {
@@ -509,8 +519,10 @@ static int rcas_dispatch_impl(const fsr1_image* in, const fsr1_image* out, const
   a.rows_below = rows_below;
   hipError_t e;
   if (flags & FSR1_FLAG_MATH_PACKED_FP16) {
-    if (in->format != FSR1_FORMAT_RGBA16F) return fail(FSR1_ERR_UNSUPPORTED, "rcas: packed-fp16 math needs RGBA16F images");
-    e = rcas_h_launch(a, static_cast<hipStream_t>(stream));
+    if (!packed_format_ok(in->format)) return fail(FSR1_ERR_UNSUPPORTED, "rcas: packed-fp16 math needs RGBA16F, RGBA8_UNORM or R10G10B10A2_UNORM images");
+    rcas_h_geometry(in->format, out->width, out->height, &a.tiles_x, &a.tiles_y);  // the H kernels' own strip shapes
+    if ((rc = check_grid("rcas", a.tiles_x, a.tiles_y, a.frames))) return rc;
+    e = rcas_h_launch(a, in->format, static_cast<hipStream_t>(stream));
   } else if (a.color.stages) {
     e = rcas_color_launch(a, in->format, out->format, (flags & FSR1_FLAG_MATH_EXACT) != 0, static_cast<hipStream_t>(stream));
   } else {
@@ -567,8 +579,8 @@ static int fused_dispatch_impl(const fsr1_image* in, const fsr1_image* out, cons
   if ((flags & FSR1_FLAG_MATH_STRICT) && (in->format == FSR1_FORMAT_RGBA32F || a.color.stages))
     flags = (flags & ~(uint32_t)FSR1_FLAG_MATH_STRICT) | FSR1_FLAG_MATH_EXACT;
   const bool packed = (flags & FSR1_FLAG_MATH_PACKED_FP16) != 0;
-  if (packed && (in->format != FSR1_FORMAT_RGBA16F || a.color.stages))
-    return fail(FSR1_ERR_UNSUPPORTED, "fused: packed-fp16 math needs RGBA16F images and runs without colour stages");
+  if (packed && (!packed_format_ok(in->format) || a.color.stages))
+    return fail(FSR1_ERR_UNSUPPORTED, "fused: packed-fp16 math needs RGBA16F, RGBA8_UNORM or R10G10B10A2_UNORM images and runs without colour stages");
   memcpy(a.easu_con, easu_con, sizeof a.easu_con);
   memcpy(a.rcas_con, rcas_con, sizeof a.rcas_con);
   float sx, sy, bx, by;
@@ -605,7 +617,7 @@ static int fused_dispatch_impl(const fsr1_image* in, const fsr1_image* out, cons
   if ((rc = check_grid("fused", a.tiles_x, a.tiles_y, a.frames))) return rc;
   a.flags = resolve_output_policy(flags, true);
   const bool exact = (flags & FSR1_FLAG_MATH_EXACT) != 0;
-  hipError_t e = packed ? (s2 ? fused_s2_h_launch(a, static_cast<hipStream_t>(stream)) : fused_h_launch(a, static_cast<hipStream_t>(stream)))
+  hipError_t e = packed ? (s2 ? fused_s2_h_launch(a, in->format, static_cast<hipStream_t>(stream)) : fused_h_launch(a, in->format, static_cast<hipStream_t>(stream)))
                  : a.color.stages ? fused_color_launch(a, in->format, out->format, exact, static_cast<hipStream_t>(stream))
                  : s2             ? fused_s2_launch(a, in->format, exact, tall, static_cast<hipStream_t>(stream), strict)
                                   : fused_launch(a, in->format, exact, static_cast<hipStream_t>(stream), strict);
@@ -684,8 +696,8 @@ static int upscale_decide(const char* who, const fsr1_image* in, bool have_inter
   if (p->flags & ~(plan->math | rcas_opts | plan->out_policy | overlap))
     return fail(FSR1_ERR_INVALID_ARGUMENT, "%s: params.flags may only hold MATH_*, RCAS_*, OUTPUT_* and FRAMES_OVERLAP bits", who);
   plan->math |= overlap;
-  if ((plan->math & FSR1_FLAG_MATH_PACKED_FP16) && (in->format != FSR1_FORMAT_RGBA16F || out->format != FSR1_FORMAT_RGBA16F || have_stages))
-    return fail(FSR1_ERR_UNSUPPORTED, "%s: packed-fp16 math needs RGBA16F images and runs without colour stages", who);
+  if ((plan->math & FSR1_FLAG_MATH_PACKED_FP16) && (!packed_format_ok(in->format) || out->format != in->format || have_stages))
+    return fail(FSR1_ERR_UNSUPPORTED, "%s: packed-fp16 math needs RGBA16F, RGBA8_UNORM or R10G10B10A2_UNORM images of one format and runs without colour stages", who);
   // :106 — viewport == input resource size == (renderWidth, renderHeight); output = display size
   FsrEasuCon(plan->easu_con, plan->easu_con + 4, plan->easu_con + 8, plan->easu_con + 12, p->render_width, p->render_height, p->render_width,
              p->render_height, (float)out->width, (float)out->height);

@@ -22,8 +22,14 @@ namespace fsr1 {
 // that shares one 12-tap window, tiles are shifted by one pixel, the footprint is a compile-time 35 x 11 and the
 // sub-texel positions are the constants 1/4 and 3/4 — see easu_kernel in fsr1_easu_kernel.h.  Same binary16 operations
 // on the same values as the generic variant: bit-identical.
-template <bool S2>
-__global__ void __launch_bounds__(kThreads) easu_h_kernel(const EasuArgs a) {
+//
+// FMT: the storage format (TexelH, fsr1_device_half.hpp).  It enters at the two ends only: phase 1's texel fetch (4 bytes per texel for
+// the 32 bpp UNORM formats, unpacked and narrowed to binary16 once per input texel) and the stores (the S2 quad writes its two row pairs
+// as 8 bytes each, the generic form 4 bytes per lane-row).  Everything between is the same instruction sequence on the same values.
+template <bool S2, int FMT>
+__device__ __forceinline__ void easu_h_tile(const EasuArgs& a) {
+  typedef TexelH<FMT> tex;
+  constexpr int kPx = (int)sizeof(typename tex::T);
   extern __shared__ __attribute__((aligned(16))) char smem[];
   constexpr int kS2W = kTileW / 2 + 3, kS2H = kTileH / 2 + 3;
   const int cap = S2 ? kS2W * kS2H : a.fp_w * a.fp_h;
@@ -47,27 +53,27 @@ __global__ void __launch_bounds__(kThreads) easu_h_kernel(const EasuArgs a) {
   if constexpr (S2) {
     static_assert(kTileW == 64 && kTileH == 16, "the exact-2x variant is built for 64 x 16 tiles");
     const int ox0 = tx * kTileW - 1, oy0 = ty * kTileH - 1;
-    easu_h_stage<kS2W, kS2H>(l, a.in, in_frame, tx * (kTileW / 2) - 2, ty * (kTileH / 2) - 2, kS2W, kS2H, tid);
+    easu_h_stage<kS2W, kS2H, kThreads, FMT>(l, a.in, in_frame, tx * (kTileW / 2) - 2, ty * (kTileH / 2) - 2, kS2W, kS2H, tid);
     const int W = a.out.width, H = a.out.height;
     const int qx = lane & 31, qy = 2 * wave + (lane >> 5);
     const int oxa = ox0 + 2 * qx, oya = oy0 + 2 * qy;  // odd: the quad is {oxa, oxa+1} x {oya, oya+1}
     const bool xin0 = oxa >= 0 && oxa < W, xin1 = oxa + 1 < W, yin0 = oya >= 0 && oya < H, yin1 = oya + 1 < H;
     if (!((xin0 || xin1) && (yin0 || yin1))) return;
     const int f = (qy + 1) * kS2W + (qx + 1);
-    char* const o0 = a.out.base + (long long)frame * a.out.frame_stride + (long long)oya * a.out.pitch + (long long)oxa * 8;
+    char* const o0 = a.out.base + (long long)frame * a.out.frame_stride + (long long)oya * a.out.pitch + (long long)oxa * kPx;
     const half_t q1 = (half_t)0.25f, q3 = (half_t)0.75f;
-    typedef TexelPair<FSR1_FORMAT_RGBA16F> pair;
+    typedef TexelPair<FMT> pair;
     if (xin0 && xin1 && yin0 && yin1) {
       const half4_t p00 = easu_h_pixel(l, f, kS2W, h2(q1, q1), hdr), p10 = easu_h_pixel(l, f, kS2W, h2(q3, q1), hdr);
       const half4_t p01 = easu_h_pixel(l, f, kS2W, h2(q1, q3), hdr), p11 = easu_h_pixel(l, f, kS2W, h2(q3, q3), hdr);
-      store_out<8>(o0, pair::make(p00, p10), stream);
-      store_out<8>(o0 + a.out.pitch, pair::make(p01, p11), stream);
+      store_out<kPx>(o0, pair::make(tex::store(p00), tex::store(p10)), stream);
+      store_out<kPx>(o0 + a.out.pitch, pair::make(tex::store(p01), tex::store(p11)), stream);
       return;
     }
     auto row = [&](char* o, bool yin, half_t ppy) {
       if (!yin) return;
-      if (xin0) store_out<8>(o, easu_h_pixel(l, f, kS2W, h2(q1, ppy), hdr), stream);
-      if (xin1) store_out<8>(o + 8, easu_h_pixel(l, f, kS2W, h2(q3, ppy), hdr), stream);
+      if (xin0) store_out<kPx>(o, tex::store(easu_h_pixel(l, f, kS2W, h2(q1, ppy), hdr)), stream);
+      if (xin1) store_out<kPx>(o + kPx, tex::store(easu_h_pixel(l, f, kS2W, h2(q3, ppy), hdr)), stream);
     };
     row(o0, yin0, q1);
     row(o0 + a.out.pitch, yin1, q3);
@@ -81,11 +87,11 @@ __global__ void __launch_bounds__(kThreads) easu_h_kernel(const EasuArgs a) {
   const int fy0 = (int)floorf((float)oy0 * c0y + c0w) - 1;
   const int fw = min((int)floorf((float)oxl * c0x + c0z) + 2 - fx0 + 1, a.fp_w);
   const int fh = min((int)floorf((float)oyl * c0y + c0w) + 2 - fy0 + 1, a.fp_h);
-  easu_h_stage<0, 0>(l, a.in, in_frame, fx0, fy0, fw, fh, tid);
+  easu_h_stage<0, 0, kThreads, FMT>(l, a.in, in_frame, fx0, fy0, fw, fh, tid);
 
   const int ox = ox0 + lane;
   if (ox >= a.out.width) return;
-  char* const out_col = a.out.base + (long long)frame * a.out.frame_stride + (size_t)ox * sizeof(half4_t);
+  char* const out_col = a.out.base + (long long)frame * a.out.frame_stride + (size_t)ox * kPx;
   float ppx = (float)ox * c0x + c0z;  // :513-515
   const float fpx = floorf(ppx);
   ppx -= fpx;
@@ -100,23 +106,47 @@ __global__ void __launch_bounds__(kThreads) easu_h_kernel(const EasuArgs a) {
     ppy -= fpy;
     const half2_t ppp = h2((half_t)ppx, (half_t)ppy);  // :516 AH2(pp), RTNE
     const int f = ((int)fpy - fy0) * fw + lx;            // footprint index of texel 'f'
-    store_out<8>(out_col + (long long)oy * a.out.pitch, easu_h_pixel(l, f, fw, ppp, hdr), stream);
+    store_out<kPx>(out_col + (long long)oy * a.out.pitch, tex::store(easu_h_pixel(l, f, fw, ppp, hdr)), stream);
   }
 }
 
-size_t easu_h_lds_bytes(int fp_w, int fp_h) { return (size_t)fp_w * fp_h * 48; }
+template <bool S2>
+__global__ void __launch_bounds__(kThreads) easu_h_kernel(const EasuArgs a) {  // RGBA16F storage
+  easu_h_tile<S2, FSR1_FORMAT_RGBA16F>(a);
+}
+template <bool S2, int FMT>
+__global__ void __launch_bounds__(kThreads) easu_h_unorm_kernel(const EasuArgs a) {  // 32 bpp UNORM storage
+  easu_h_tile<S2, FMT>(a);
+}
 
-// s2: launch the exact-2x variant (the caller has checked con0 and laid the grid out for the shifted tiles).
-hipError_t easu_h_launch(const EasuArgs& a, bool s2, hipStream_t stream) {
+// The LDS records are binary16 whatever the storage format: 48 bytes per footprint texel.
+size_t easu_h_lds_bytes(int fp_w, int fp_h) { return (size_t)fp_w * fp_h * kEasuHLdsPerTexel; }
+
+namespace {
+template <class K>
+hipError_t easu_h_launch_one(K kernel, const EasuArgs& a, bool s2, hipStream_t stream) {
   const dim3 grid((unsigned)(a.tiles_x * a.tiles_y * a.frames)), block(kThreads);
   const size_t lds = easu_h_lds_bytes(a.fp_w, a.fp_h);
-  if (s2) {
-    hipLaunchKernelGGL(easu_h_kernel<true>, grid, block, lds, stream, a);
-    return hipGetLastError();
-  }
-  if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(&easu_h_kernel<false>), lds); e != hipSuccess) return e;
-  hipLaunchKernelGGL(easu_h_kernel<false>, grid, block, lds, stream, a);
+  if (!s2)  // (the exact-2x footprint is 18.5 KB)
+    if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(kernel), lds); e != hipSuccess) return e;
+  hipLaunchKernelGGL(kernel, grid, block, lds, stream, a);
   return hipGetLastError();
+}
+}  // namespace
+
+// s2: launch the exact-2x variant (the caller has checked con0 and laid the grid out for the shifted tiles).
+hipError_t easu_h_launch(const EasuArgs& a, int fmt, bool s2, hipStream_t stream) {
+  switch (fmt) {
+    case FSR1_FORMAT_RGBA16F:
+      return s2 ? easu_h_launch_one(&easu_h_kernel<true>, a, true, stream) : easu_h_launch_one(&easu_h_kernel<false>, a, false, stream);
+    case FSR1_FORMAT_RGBA8_UNORM:
+      return s2 ? easu_h_launch_one(&easu_h_unorm_kernel<true, FSR1_FORMAT_RGBA8_UNORM>, a, true, stream)
+                : easu_h_launch_one(&easu_h_unorm_kernel<false, FSR1_FORMAT_RGBA8_UNORM>, a, false, stream);
+    case FSR1_FORMAT_R10G10B10A2_UNORM:
+      return s2 ? easu_h_launch_one(&easu_h_unorm_kernel<true, FSR1_FORMAT_R10G10B10A2_UNORM>, a, true, stream)
+                : easu_h_launch_one(&easu_h_unorm_kernel<false, FSR1_FORMAT_R10G10B10A2_UNORM>, a, false, stream);
+    default: return hipErrorInvalidValue;
+  }
 }
 
 }  // namespace fsr1

@@ -16,8 +16,13 @@ constexpr int kMidW = kTileW + 2;
 constexpr int kMidH = kFusedTileH + 2;
 }  // namespace
 
-template <bool OPTS>
+// FMT: the storage format (TexelH).  For the 32 bpp UNORM formats the staging fetches 4-byte texels, every EASU result passes through
+// the store rule and then the load rule on its way into the LDS tile — the values the two dispatches would have written to and read back
+// from an intermediary of the output's format — and the output goes through the store rule, 4 bytes per lane-row.
+template <bool OPTS, int FMT>
 __global__ void __launch_bounds__(kThreads) fused_h_kernel(const FusedArgs a) {
+  typedef TexelH<FMT> tex;
+  constexpr int kPx = (int)sizeof(typename tex::T);
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int cap = a.fp_w * a.fp_h;
   const EasuHLds l = easu_h_lds_carve(smem, cap);
@@ -40,7 +45,7 @@ __global__ void __launch_bounds__(kThreads) fused_h_kernel(const FusedArgs a) {
   const int fw = min((int)floorf((float)axl * c0x + c0z) + 2 - fx0 + 1, a.fp_w);
   const int fh = min((int)floorf((float)ayl * c0y + c0w) + 2 - fy0 + 1, a.fp_h);
   const int tid = threadIdx.x;
-  easu_h_stage<0, 0>(l, a.in, a.in.base + (long long)frame * a.in.frame_stride, fx0, fy0, fw, fh, tid);
+  easu_h_stage<0, 0, kThreads, FMT>(l, a.in, a.in.base + (long long)frame * a.in.frame_stride, fx0, fy0, fw, fh, tid);
 
   // ---- phase 3: FsrEasuH on the apron tile -> LDS (EASU runs with Sample.x = 0 when RCAS follows, FSR_Filter.cpp:107) ----
   const int lane = tid & 63, wave = tid >> 6;
@@ -55,7 +60,7 @@ __global__ void __launch_bounds__(kThreads) fused_h_kernel(const FusedArgs a) {
       const int f = ((int)fpy - fy0) * fw + ((int)fpx - fx0);
       px = easu_h_pixel(l, f, fw, h2((half_t)ppx, (half_t)ppy), false);
     }
-    mid[my * kMidW + mx] = px;
+    mid[my * kMidW + mx] = tex::requant(px);
   };
 #pragma unroll 1
   for (int my = wave; my < kMidH; my += 4) easu_to_mid(lane, my);
@@ -70,7 +75,7 @@ __global__ void __launch_bounds__(kThreads) fused_h_kernel(const FusedArgs a) {
   const bool stream = (a.flags & FSR1_FLAG_OUTPUT_STREAMING) != 0;
   const half_t sharp1 = __builtin_bit_cast(half_t, (u16)(a.rcas_con[1] & 0xffffu));  // :857
   const int ox = ox0 + lane;
-  char* const out_col = a.out.base + (long long)frame * a.out.frame_stride + (long long)ox * 8;
+  char* const out_col = a.out.base + (long long)frame * a.out.frame_stride + (long long)ox * kPx;
   const half_t one = (half_t)1.0f;
 #pragma unroll
   for (int p = 0; p < kFusedTileH / 8; ++p) {
@@ -86,26 +91,39 @@ __global__ void __launch_bounds__(kThreads) fused_h_kernel(const FusedArgs a) {
                                      sharp1, flags);
     const bool alpha = (flags & FSR1_FLAG_RCAS_PASSTHROUGH_ALPHA) != 0;  // :905-907 / FSR_Pass.hlsl:94
     const int oy = oy0 + r;
-    if (ox < W && oy < H) store_out<8>(out_col + (long long)oy * a.out.pitch, half4_t{px.r.x, px.g.x, px.b.x, alpha ? e0.w : one}, stream);
-    if (ox < W && oy + 1 < H) store_out<8>(out_col + (long long)(oy + 1) * a.out.pitch, half4_t{px.r.y, px.g.y, px.b.y, alpha ? e1.w : one}, stream);
+    if (ox < W && oy < H) store_out<kPx>(out_col + (long long)oy * a.out.pitch, tex::store(half4_t{px.r.x, px.g.x, px.b.x, alpha ? e0.w : one}), stream);
+    if (ox < W && oy + 1 < H) store_out<kPx>(out_col + (long long)(oy + 1) * a.out.pitch, tex::store(half4_t{px.r.y, px.g.y, px.b.y, alpha ? e1.w : one}), stream);
   }
 }
 
+// (binary16 records and a binary16 tile whatever the storage format)
 size_t fused_h_lds_bytes(int fp_w, int fp_h) { return (size_t)fp_w * fp_h * kEasuHLdsPerTexel + (size_t)kMidW * kMidH * sizeof(half4_t); }
 
-hipError_t fused_h_launch(const FusedArgs& a, hipStream_t stream) {
+namespace {
+template <int FMT>
+hipError_t fused_h_launch_fmt(const FusedArgs& a, hipStream_t stream) {
   static_assert(kFusedTileH % 8 == 0, "a wave's rows are processed in vertical pairs");
   const dim3 grid((unsigned)(a.tiles_x * a.tiles_y * a.frames)), block(kThreads);
   const size_t lds = fused_h_lds_bytes(a.fp_w, a.fp_h);
   const bool opts = (a.flags & (FSR1_FLAG_RCAS_DENOISE | FSR1_FLAG_RCAS_PASSTHROUGH_ALPHA | FSR1_FLAG_HDR_SQUARE)) != 0;
   if (opts) {
-    if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(&fused_h_kernel<true>), lds); e != hipSuccess) return e;
-    hipLaunchKernelGGL(fused_h_kernel<true>, grid, block, lds, stream, a);
+    if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(&fused_h_kernel<true, FMT>), lds); e != hipSuccess) return e;
+    hipLaunchKernelGGL((fused_h_kernel<true, FMT>), grid, block, lds, stream, a);
   } else {
-    if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(&fused_h_kernel<false>), lds); e != hipSuccess) return e;
-    hipLaunchKernelGGL(fused_h_kernel<false>, grid, block, lds, stream, a);
+    if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(&fused_h_kernel<false, FMT>), lds); e != hipSuccess) return e;
+    hipLaunchKernelGGL((fused_h_kernel<false, FMT>), grid, block, lds, stream, a);
   }
   return hipGetLastError();
+}
+}  // namespace
+
+hipError_t fused_h_launch(const FusedArgs& a, int fmt, hipStream_t stream) {
+  switch (fmt) {
+    case FSR1_FORMAT_RGBA16F: return fused_h_launch_fmt<FSR1_FORMAT_RGBA16F>(a, stream);
+    case FSR1_FORMAT_RGBA8_UNORM: return fused_h_launch_fmt<FSR1_FORMAT_RGBA8_UNORM>(a, stream);
+    case FSR1_FORMAT_R10G10B10A2_UNORM: return fused_h_launch_fmt<FSR1_FORMAT_R10G10B10A2_UNORM>(a, stream);
+    default: return hipErrorInvalidValue;
+  }
 }
 
 }  // namespace fsr1

@@ -26,8 +26,12 @@ __device__ __forceinline__ half2_t dpp2(half2_t keep, half2_t v) {
 size_t fused_s2_h_lds_bytes() { return (size_t)kFs2FpW * kFs2FpH * kEasuHLdsPerTexel + (size_t)kFs2MidW * kFs2Ring * sizeof(half4_t); }
 
 // OPTS = false: plain pass (no denoise / alpha pass-through / HDR square), flags compiled out.  RUN = false: the one-step launch.
-template <bool OPTS, bool RUN>
+// FMT: the storage format (TexelH) — 4-byte texel fetches, the ring holds store-then-load requantised values and the output goes through
+// the store rule for the 32 bpp UNORM formats, as in fused_h_kernel.
+template <bool OPTS, bool RUN, int FMT>
 __global__ void __launch_bounds__(kThreads) fused_s2_h_kernel(const FusedArgs a) {
+  typedef TexelH<FMT> tex;
+  constexpr int kPx = (int)sizeof(typename tex::T);
   static_assert(kFs2QH == 8 && kThreads == 256, "32 x 8 quads over 256 lanes");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const EasuHLds l = easu_h_lds_carve(smem, kFs2FpW * kFs2FpH);
@@ -59,7 +63,7 @@ __global__ void __launch_bounds__(kThreads) fused_s2_h_kernel(const FusedArgs a)
   for (int s = 0; s < steps; ++s) {
     const int ay0 = Y0 - 1 + kFs2Step * s;  // first EASU row of this step
     const int tid = threadIdx.x, lane = tid & 63;
-    easu_h_stage<kFs2FpW, kFs2FpH>(l, a.in, in_frame, 31 * tx - 2, ((ay0 + 1) >> 1) - 2, kFs2FpW, kFs2FpH, tid);
+    easu_h_stage<kFs2FpW, kFs2FpH, kThreads, FMT>(l, a.in, in_frame, 31 * tx - 2, ((ay0 + 1) >> 1) - 2, kFs2FpW, kFs2FpH, tid);
     // (its two barriers also separate this step's ring writes from the previous step's RCAS reads)
 
     // ---- phase 3: FsrEasuH on the step's 64 x 16 pixels, a quad per lane (EASU runs with Sample.x = 0 when RCAS follows:
@@ -84,8 +88,8 @@ __global__ void __launch_bounds__(kThreads) fused_s2_h_kernel(const FusedArgs a)
         if (xin0 && yin1) p01 = easu_h_pixel(l, f, kFs2FpW, h2(q1, q3), false);
         if (xin1 && yin1) p11 = easu_h_pixel(l, f, kFs2FpW, h2(q3, q3), false);
       }
-      *reinterpret_cast<pair::T*>(m0) = pair::make(p00, p10);
-      *reinterpret_cast<pair::T*>(m0 + kFs2MidW) = pair::make(p01, p11);
+      *reinterpret_cast<pair::T*>(m0) = pair::make(tex::requant(p00), tex::requant(p10));
+      *reinterpret_cast<pair::T*>(m0 + kFs2MidW) = pair::make(tex::requant(p01), tex::requant(p11));
     }
     __syncthreads();
 
@@ -96,7 +100,7 @@ __global__ void __launch_bounds__(kThreads) fused_s2_h_kernel(const FusedArgs a)
     {
       const int ox = ax0 + lane;
       const bool col_ok = lane >= 1 && lane <= kFs2OutW && ox < W;
-      const uint32_t col_off = (uint32_t)ox * 8u;  // (never used when ox < 0: lane 0 stores nothing)
+      const uint32_t col_off = (uint32_t)ox * (uint32_t)kPx;  // (never used when ox < 0: lane 0 stores nothing)
       auto row = [&](int j) {  // (wave-uniform slot)
         int slot = base + j;
         slot -= slot >= kFs2Ring ? kFs2Ring : 0;
@@ -114,9 +118,9 @@ __global__ void __launch_bounds__(kThreads) fused_s2_h_kernel(const FusedArgs a)
         const bool alpha = (flags & FSR1_FLAG_RCAS_PASSTHROUGH_ALPHA) != 0;  // :905-907 / FSR_Pass.hlsl:94
         const int oy = ay0 + j - 2;
         if (col_ok && oy < H)
-          store_out<8>(out_frame + (long long)oy * a.out.pitch + col_off, half4_t{px.r.x, px.g.x, px.b.x, alpha ? e0.w : one}, stream);
+          store_out<kPx>(out_frame + (long long)oy * a.out.pitch + col_off, tex::store(half4_t{px.r.x, px.g.x, px.b.x, alpha ? e0.w : one}), stream);
         if (col_ok && oy + 1 < H)
-          store_out<8>(out_frame + (long long)(oy + 1) * a.out.pitch + col_off, half4_t{px.r.y, px.g.y, px.b.y, alpha ? e1.w : one}, stream);
+          store_out<kPx>(out_frame + (long long)(oy + 1) * a.out.pitch + col_off, tex::store(half4_t{px.r.y, px.g.y, px.b.y, alpha ? e1.w : one}), stream);
       };
       const int j0 = 1 + 4 * wave;
       if (!(s == 0 && wave == 0)) do_pair(j0);  // wave-uniform
@@ -128,18 +132,30 @@ __global__ void __launch_bounds__(kThreads) fused_s2_h_kernel(const FusedArgs a)
   }
 }
 
-hipError_t fused_s2_h_launch(const FusedArgs& a, hipStream_t stream) {
+namespace {
+template <int FMT>
+hipError_t fused_s2_h_launch_fmt(const FusedArgs& a, hipStream_t stream) {
   const dim3 grid((unsigned)(a.tiles_x * a.tiles_y * a.frames)), block(kThreads);
   const size_t lds = fused_s2_h_lds_bytes();
   const bool opts = (a.flags & (FSR1_FLAG_RCAS_DENOISE | FSR1_FLAG_RCAS_PASSTHROUGH_ALPHA | FSR1_FLAG_HDR_SQUARE)) != 0;
   if (a.run_steps > 1) {
-    if (opts) hipLaunchKernelGGL((fused_s2_h_kernel<true, true>), grid, block, lds, stream, a);
-    else hipLaunchKernelGGL((fused_s2_h_kernel<false, true>), grid, block, lds, stream, a);
+    if (opts) hipLaunchKernelGGL((fused_s2_h_kernel<true, true, FMT>), grid, block, lds, stream, a);
+    else hipLaunchKernelGGL((fused_s2_h_kernel<false, true, FMT>), grid, block, lds, stream, a);
   } else {
-    if (opts) hipLaunchKernelGGL((fused_s2_h_kernel<true, false>), grid, block, lds, stream, a);
-    else hipLaunchKernelGGL((fused_s2_h_kernel<false, false>), grid, block, lds, stream, a);
+    if (opts) hipLaunchKernelGGL((fused_s2_h_kernel<true, false, FMT>), grid, block, lds, stream, a);
+    else hipLaunchKernelGGL((fused_s2_h_kernel<false, false, FMT>), grid, block, lds, stream, a);
   }
   return hipGetLastError();
+}
+}  // namespace
+
+hipError_t fused_s2_h_launch(const FusedArgs& a, int fmt, hipStream_t stream) {
+  switch (fmt) {
+    case FSR1_FORMAT_RGBA16F: return fused_s2_h_launch_fmt<FSR1_FORMAT_RGBA16F>(a, stream);
+    case FSR1_FORMAT_RGBA8_UNORM: return fused_s2_h_launch_fmt<FSR1_FORMAT_RGBA8_UNORM>(a, stream);
+    case FSR1_FORMAT_R10G10B10A2_UNORM: return fused_s2_h_launch_fmt<FSR1_FORMAT_R10G10B10A2_UNORM>(a, stream);
+    default: return hipErrorInvalidValue;
+  }
 }
 
 }  // namespace fsr1

@@ -10,6 +10,8 @@
 // rows flow through registers (b = previous row, h = next row), the horizontal neighbours of a lane's
 // pixel pair are its own other pixel and the adjacent lane's facing pixel (DPP wave shift); lanes 0 / 63
 // also load the strip's apron column.  Loads outside the image are 0 (FSR_Pass.hlsl:61).
+// That is the RGBA16F kernel (rcas_h_kernel); the 32 bpp UNORM formats have a strip shape of their own, four pixels per lane
+// (rcas_h4_kernel, below).
 #include "fsr1_device.h"
 #include "fsr1_device_half.hpp"
 
@@ -125,16 +127,157 @@ __global__ void __launch_bounds__(kRcasHThreads) rcas_h_kernel(const RcasArgs a)
   }
 }
 
-void rcas_h_geometry(int width, int height, int* tiles_x, int* tiles_y) {
-  *tiles_x = (width + kRcasHCols - 1) / kRcasHCols;
-  *tiles_y = (height + kRcasHRows - 1) / kRcasHRows;
+// ---- 32 bpp UNORM storage (FSR1_FORMAT_RGBA8_UNORM, FSR1_FORMAT_R10G10B10A2_UNORM): FOUR adjacent pixels per lane ----
+// 16-byte accesses are what this chip moves at full rate (above): at 4 bytes per pixel a lane therefore owns four pixels — one 16-byte load and one 16-byte store per lane-row — and a wave covers 256 columns.  A lane makes two
+// rcas_pixel_h2 evaluations per row, on the pairs (p0, p1) and (p2, p3).  Their horizontal taps
+//     d(p0,p1) = (left lane's p3, p0)     f(p0,p1) = (p1, p2) = d(p2,p3)     f(p2,p3) = (p3, right lane's p0)
+// come from the lane's own registers except for two values, which cross by DPP wave shifts (three channels each: six v_mov_dpp per
+// four pixels, where the two-pixel kernel spends six per two); lanes 0 / 63 load the strip's apron texel.
+// Rows wait in the ring (kAhead rows in flight) as the codes they were loaded as — four registers and the apron's one — and are
+// narrowed to binary16 pairs once, when they become the row below the centre; the centre and the row above are carried in registers.
+// Alpha travels as the centre's code bits and only when FSR1_FLAG_RCAS_PASSTHROUGH_ALPHA asks for it (store(load(code)) == code for
+// every code, fsr1_device_half.hpp), otherwise it is the constant maximum code: no alpha channel is ever converted.
+// Strip shape: 8 rows, the RGBA16F kernel's measured optimum — the row above and the row below are read again by the neighbouring
+// strips (+25 % of loads, cache hits for the most part), 16 rows and more lose more to the shorter grid than the apron saves, and a
+// 4K image is 15 x 270 = 4050 waves, each with three 1 KB row loads in flight (12 MB outstanding: beyond the latency x bandwidth product
+// of the memory system).  Two waves per workgroup, side by side, as in the other RCAS kernels; a wave whose 256 columns start beyond the
+// image leaves at once.  Measured at 4K (profiles/unorm_h_1080p_to_4k.json, us): RGBA8 31.6 against the RGBA16F kernel's 32.3 in the
+// same run — half the bytes, 2 % less time: with 16-byte accesses the pass is bound by the packed arithmetic (2.1 TB/s), not by memory.
+// Other strip heights and a two-pixel / 8-byte form are unmeasured.
+constexpr int kRcasH4Rows = 8;
+constexpr int kRcasH4Waves = 2;
+constexpr int kRcasH4Threads = 64 * kRcasH4Waves;
+constexpr int kRcasH4WaveCols = 4 * 64;
+constexpr int kRcasH4Cols = kRcasH4WaveCols * kRcasH4Waves;
+
+template <int FMT, bool OPTS>
+__global__ void __launch_bounds__(kRcasH4Threads) rcas_h4_kernel(const RcasArgs a) {
+  typedef TexelH<FMT> tex;
+  typedef uint32_t quad_t __attribute__((ext_vector_type(4), aligned(4)));  // four texels: rows are only texel-aligned
+  const uint32_t flags = OPTS ? a.flags : 0u;
+  const bool stream = (a.flags & FSR1_FLAG_OUTPUT_STREAMING) != 0;
+  const int tiles_per_frame = a.tiles_x * a.tiles_y;
+  const int t = xcd_swizzle(blockIdx.x, tiles_per_frame * a.frames, a.xcd_shift);
+  const int frame = t / tiles_per_frame;
+  const int tf = t - frame * tiles_per_frame;
+  const int ty = tf / a.tiles_x, tx = tf - ty * a.tiles_x;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int x0 = tx * kRcasH4Cols + wave * kRcasH4WaveCols, y0 = ty * kRcasH4Rows;
+  if (x0 >= a.in.width) return;
+
+  const int W = a.in.width, H = a.in.height;
+  const int col = x0 + 4 * lane;
+  const int nok = min(max(W - col, 0), 4);  // this lane's pixels inside the image: 4 but at a ragged right edge
+  const int hcol = lane == 0 ? x0 - 1 : x0 + kRcasH4WaveCols;
+  const bool halo_ok = (lane == 0 || lane == 63) && hcol >= 0 && hcol < W;
+  const char* const in_frame = a.in.base + (long long)frame * a.in.frame_stride;
+  char* const out_frame = a.out.base + (long long)frame * a.out.frame_stride;
+
+  // a row's address = wave-uniform 64-bit row base + a 32-bit lane offset (see rcas_strip in fsr1_rcas_kernel.h)
+  const uint32_t off = (uint32_t)col * 4u, hoff = (uint32_t)max(hcol, 0) * 4u;
+  auto zext = [](uint32_t o) { asm("" : "+v"(o)); return (size_t)o; };
+  struct raw_t { quad_t own; uint32_t halo; };
+  // one row of this lane's four texels and the apron texel, as stored; code 0 (= 0.0 in every channel) outside the image (FSR_Pass.hlsl:61)
+  auto load = [&](int y, raw_t& r) {
+    quad_t p = {0u, 0u, 0u, 0u};
+    uint32_t ph = 0u;
+    if (y >= 0 && y < H) {  // wave-uniform
+      const char* const row = in_frame + (long long)y * a.in.pitch;
+      if (nok == 4) {
+        p = *reinterpret_cast<const quad_t*>(row + zext(off));
+      } else if (nok > 0) {
+        const uint32_t* const px = reinterpret_cast<const uint32_t*>(row + zext(off));
+        p.x = px[0];
+        if (nok > 1) p.y = px[1];
+        if (nok > 2) p.z = px[2];
+      }
+      if (halo_ok) ph = *reinterpret_cast<const uint32_t*>(row + zext(hoff));
+    }
+    r.own = p;
+    r.halo = ph;
+  };
+  struct row_t { rgbh2_t lo, hi; };  // (p0, p1) and (p2, p3)
+  auto narrow = [](const quad_t& p) { return row_t{tex::load_rgb2(p.x, p.y), tex::load_rgb2(p.z, p.w)}; };
+
+  constexpr int kAhead = 3, kRing = kAhead + 1;
+  raw_t q[kRing];
+  row_t b, e;
+  {
+    raw_t above;
+    load(y0 - 1, above);
+#pragma unroll
+    for (int k = 0; k < kAhead; ++k) load(y0 + k, q[k]);
+    b = narrow(above.own);
+    e = narrow(q[0].own);
+  }
+  // :857 sharpness = AH2_AU1(con.y).x — the packed half of con[1]
+  const half_t sharp1 = __builtin_bit_cast(half_t, (u16)(a.con[1] & 0xffffu));
+
+  static_assert(kRcasH4Rows % kRing == 0, "strips are a multiple of the ring tall");
+  // unrolled by the ring (static ring indices), rolled beyond that: see rcas_h_kernel
+#pragma unroll 1
+  for (int r0 = 0; r0 < kRcasH4Rows; r0 += kRing)
+#pragma unroll
+  for (int k = 0; k < kRing; ++k) {
+    const int y = y0 + r0 + k;
+    // (past the row below the strip nothing is needed: that row is read again — a cache hit — instead of two more rows per strip)
+    load(min(y + kAhead, y0 + kRcasH4Rows), q[(k + kAhead) % kRing]);
+    const row_t h = narrow(q[(k + 1) % kRing].own);
+    const quad_t centre = q[k % kRing].own;
+    const rgbh2_t eh = tex::load_rgb2(q[k % kRing].halo, q[k % kRing].halo);  // the apron texel in both halves (lanes 0 / 63)
+    // the two values from the neighbouring lanes: .y of nl = the left lane's p3, .x of nr = the right lane's p0
+    const half2_t nlR = dpp2<kShr1>(eh.r, e.hi.r), nlG = dpp2<kShr1>(eh.g, e.hi.g), nlB = dpp2<kShr1>(eh.b, e.hi.b);
+    const half2_t nrR = dpp2<kShl1>(eh.r, e.lo.r), nrG = dpp2<kShl1>(eh.g, e.lo.g), nrB = dpp2<kShl1>(eh.b, e.lo.b);
+    const half2_t dR = {nlR.y, e.lo.r.x}, dG = {nlG.y, e.lo.g.x}, dB = {nlB.y, e.lo.b.x};   // left of (p0, p1)
+    const half2_t mR = {e.lo.r.y, e.hi.r.x}, mG = {e.lo.g.y, e.hi.g.x}, mB = {e.lo.b.y, e.hi.b.x};  // (p1, p2): right of (p0, p1), left of (p2, p3)
+    const half2_t fR = {e.hi.r.y, nrR.x}, fG = {e.hi.g.y, nrG.x}, fB = {e.hi.b.y, nrB.x};   // right of (p2, p3)
+    const rgbh2_t lo = rcas_pixel_h2(b.lo.r, b.lo.g, b.lo.b, dR, dG, dB, e.lo.r, e.lo.g, e.lo.b, mR, mG, mB, h.lo.r, h.lo.g, h.lo.b, sharp1, flags);
+    const rgbh2_t hi = rcas_pixel_h2(b.hi.r, b.hi.g, b.hi.b, mR, mG, mB, e.hi.r, e.hi.g, e.hi.b, fR, fG, fB, h.hi.r, h.hi.g, h.hi.b, sharp1, flags);
+    if (y < H && nok > 0) {  // (y < H: wave-uniform)
+      // alpha: the centre's own code, or the maximum code (:905-907 / FSR_Pass.hlsl:94)
+      const bool pass_alpha = (flags & FSR1_FLAG_RCAS_PASSTHROUGH_ALPHA) != 0;
+      const quad_t alpha = pass_alpha ? (quad_t)(centre & tex::kAlphaMask) : quad_t{tex::kAlphaMask, tex::kAlphaMask, tex::kAlphaMask, tex::kAlphaMask};
+      const quad_t o = quad_t{tex::store_rgb(lo.r.x, lo.g.x, lo.b.x), tex::store_rgb(lo.r.y, lo.g.y, lo.b.y),
+                              tex::store_rgb(hi.r.x, hi.g.x, hi.b.x), tex::store_rgb(hi.r.y, hi.g.y, hi.b.y)} | alpha;
+      char* const row = out_frame + (long long)y * a.out.pitch + zext(off);
+      if (nok == 4) {
+        store_out<4>(row, o, stream);
+      } else {  // ragged right edge: 1 - 3 pixels, a texel at a time
+        store_out<4>(row, (uint32_t)o.x, stream);
+        if (nok > 1) store_out<4>(row + 4, (uint32_t)o.y, stream);
+        if (nok > 2) store_out<4>(row + 8, (uint32_t)o.z, stream);
+      }
+    }
+    b = e;
+    e = h;
+  }
 }
 
-hipError_t rcas_h_launch(const RcasArgs& a0, hipStream_t stream) {
+// fmt: RGBA16F takes the two-pixel strips, the 32 bpp UNORM formats the four-pixel strips
+void rcas_h_geometry(int fmt, int width, int height, int* tiles_x, int* tiles_y) {
+  const int cols = fmt == FSR1_FORMAT_RGBA16F ? kRcasHCols : kRcasH4Cols, rows = fmt == FSR1_FORMAT_RGBA16F ? kRcasHRows : kRcasH4Rows;
+  *tiles_x = (width + cols - 1) / cols;
+  *tiles_y = (height + rows - 1) / rows;
+}
+
+namespace {
+template <int FMT>
+hipError_t rcas_h4_launch(const RcasArgs& a, bool opts, hipStream_t stream) {
+  const dim3 grid((unsigned)(a.tiles_x * a.tiles_y * a.frames)), block(kRcasH4Threads);
+  if (opts) hipLaunchKernelGGL((rcas_h4_kernel<FMT, true>), grid, block, 0, stream, a);
+  else hipLaunchKernelGGL((rcas_h4_kernel<FMT, false>), grid, block, 0, stream, a);
+  return hipGetLastError();
+}
+}  // namespace
+
+hipError_t rcas_h_launch(const RcasArgs& a0, int fmt, hipStream_t stream) {
   RcasArgs a = a0;
-  rcas_h_geometry(a.in.width, a.in.height, &a.tiles_x, &a.tiles_y);  // its own strip shape (two pixels per lane)
-  const dim3 grid((unsigned)(a.tiles_x * a.tiles_y * a.frames)), block(kRcasHThreads);
+  rcas_h_geometry(fmt, a.in.width, a.in.height, &a.tiles_x, &a.tiles_y);  // its own strip shapes (two / four pixels per lane)
   const bool opts = (a.flags & (FSR1_FLAG_RCAS_DENOISE | FSR1_FLAG_RCAS_PASSTHROUGH_ALPHA | FSR1_FLAG_HDR_SQUARE)) != 0;
+  if (fmt == FSR1_FORMAT_RGBA8_UNORM) return rcas_h4_launch<FSR1_FORMAT_RGBA8_UNORM>(a, opts, stream);
+  if (fmt == FSR1_FORMAT_R10G10B10A2_UNORM) return rcas_h4_launch<FSR1_FORMAT_R10G10B10A2_UNORM>(a, opts, stream);
+  if (fmt != FSR1_FORMAT_RGBA16F) return hipErrorInvalidValue;
+  const dim3 grid((unsigned)(a.tiles_x * a.tiles_y * a.frames)), block(kRcasHThreads);
   if (opts) hipLaunchKernelGGL(rcas_h_kernel<true>, grid, block, 0, stream, a);
   else hipLaunchKernelGGL(rcas_h_kernel<false>, grid, block, 0, stream, a);
   return hipGetLastError();

@@ -138,6 +138,62 @@ __device__ __forceinline__ rgbh_t easu_filter_h(const Ana& ana, const PairFn& pa
   return rgbh_t{hmin1(bothR.y, hmax1(-bothR.x, aR * rW)), hmin1(bothG.y, hmax1(-bothG.x, aG * rW)), hmin1(bothB.y, hmax1(-bothB.x, aB * rW))};
 }
 
+// ---- storage formats of the H kernels: what a texel fetch delivers to the binary16 arithmetic (`AH4`) and what a store takes ----
+// RGBA16F: the stored binary16 values themselves.  32 bpp UNORM (include/fsr1_hip.h, "Storage formats"): the load is the binary32
+// decode `code / (2^n - 1)` (correctly rounded) rounded once more to binary16, RTNE — what a UNORM view read as AH4 delivers.  For every
+// one of the 256 + 1024 + 4 codes that double rounding equals RTNE of the exact quotient, and so do the binary32 product
+// code * fl(1 / (2^n - 1)) narrowed RTNE and the single rounding of that exact product to binary16 (checked exhaustively on the CPU),
+// so the load is one multiply and one conversion whichever of the two the compiler forms.  The store widens the binary16 result
+// (exact) and applies Pixel<FMT>::store: (uint) fma(clamp(x,0,1), 2^n - 1, 0.5), NaN -> 0.  store(load(code)) == code for every code,
+// so an alpha channel that passes through travels as its code.
+template <int N>
+__device__ __forceinline__ float unorm_scaled(uint32_t code) { return (float)code * (1.0f / (float)N); }
+__device__ __forceinline__ half2_t pk_half(float a, float b) { return __builtin_convertvector(float2_t{a, b}, half2_t); }  // v_cvt_pk_f16_f32, RTNE
+
+struct rgbh2_t { half2_t r, g, b; };  // R, G, B of two pixels (.x / .y)
+
+template <int FMT> struct TexelH;
+template <> struct TexelH<FSR1_FORMAT_RGBA16F> {
+  typedef half4_t T;
+  static __device__ __forceinline__ half4_t load(const T& p) { return p; }
+  static __device__ __forceinline__ T store(half4_t p) { return p; }
+  static __device__ __forceinline__ half4_t requant(half4_t p) { return p; }
+};
+template <> struct TexelH<FSR1_FORMAT_RGBA8_UNORM> {
+  typedef uint32_t T;
+  static constexpr uint32_t kAlphaMask = 0xff000000u;
+  static __device__ __forceinline__ rgbh2_t load_rgb2(T p, T q) {  // two texels' colour channels as pairs
+    return rgbh2_t{pk_half(unorm_scaled<255>(p & 0xffu), unorm_scaled<255>(q & 0xffu)),
+                   pk_half(unorm_scaled<255>((p >> 8) & 0xffu), unorm_scaled<255>((q >> 8) & 0xffu)),
+                   pk_half(unorm_scaled<255>((p >> 16) & 0xffu), unorm_scaled<255>((q >> 16) & 0xffu))};
+  }
+  static __device__ __forceinline__ half4_t load(const T& p) {
+    const half2_t rg = pk_half(unorm_scaled<255>(p & 0xffu), unorm_scaled<255>((p >> 8) & 0xffu));
+    const half2_t ba = pk_half(unorm_scaled<255>((p >> 16) & 0xffu), unorm_scaled<255>(p >> 24));
+    return half4_t{rg.x, rg.y, ba.x, ba.y};
+  }
+  static __device__ __forceinline__ T store_rgb(half_t r, half_t g, half_t b) { return Pixel<FSR1_FORMAT_RGBA8_UNORM>::store((float)r, (float)g, (float)b, 0.0f); }
+  static __device__ __forceinline__ T store(half4_t p) { return Pixel<FSR1_FORMAT_RGBA8_UNORM>::store((float)p.x, (float)p.y, (float)p.z, (float)p.w); }
+  static __device__ __forceinline__ half4_t requant(half4_t p) { return load(store(p)); }
+};
+template <> struct TexelH<FSR1_FORMAT_R10G10B10A2_UNORM> {
+  typedef uint32_t T;
+  static constexpr uint32_t kAlphaMask = 0xc0000000u;
+  static __device__ __forceinline__ rgbh2_t load_rgb2(T p, T q) {
+    return rgbh2_t{pk_half(unorm_scaled<1023>(p & 0x3ffu), unorm_scaled<1023>(q & 0x3ffu)),
+                   pk_half(unorm_scaled<1023>((p >> 10) & 0x3ffu), unorm_scaled<1023>((q >> 10) & 0x3ffu)),
+                   pk_half(unorm_scaled<1023>((p >> 20) & 0x3ffu), unorm_scaled<1023>((q >> 20) & 0x3ffu))};
+  }
+  static __device__ __forceinline__ half4_t load(const T& p) {
+    const half2_t rg = pk_half(unorm_scaled<1023>(p & 0x3ffu), unorm_scaled<1023>((p >> 10) & 0x3ffu));
+    const half2_t ba = pk_half(unorm_scaled<1023>((p >> 20) & 0x3ffu), unorm_scaled<3>(p >> 30));
+    return half4_t{rg.x, rg.y, ba.x, ba.y};
+  }
+  static __device__ __forceinline__ T store_rgb(half_t r, half_t g, half_t b) { return Pixel<FSR1_FORMAT_R10G10B10A2_UNORM>::store((float)r, (float)g, (float)b, 0.0f); }
+  static __device__ __forceinline__ T store(half4_t p) { return Pixel<FSR1_FORMAT_R10G10B10A2_UNORM>::store((float)p.x, (float)p.y, (float)p.z, (float)p.w); }
+  static __device__ __forceinline__ half4_t requant(half4_t p) { return load(store(p)); }
+};
+
 // ---- the LDS-staged form of FsrEasuH (what the library's H kernels run) ----
 // LDS per footprint texel (48 bytes):
 //   tex1  half4  R G B luma of the texel                                   (phase 1; luma = B*0.5 + (R*0.5 + G), :535-538)
@@ -154,8 +210,9 @@ struct EasuHLds {
 };
 
 // Phases 1 and 2 of the H kernel for the footprint [fx0, fx0+fw) x [fy0, fy0+fh).  FW, FH: compile-time extent (exact 2x).
-// THREADS: threads of the workgroup, all of which must make the call (it contains two barriers).
-template <int FW, int FH, int THREADS = 256>
+// THREADS: threads of the workgroup, all of which must make the call (it contains two barriers).  FMT: the image's storage format
+// (TexelH): only phase 1 sees it — the LDS records, and with them phase 2 and easu_h_pixel, are the same for every format.
+template <int FW, int FH, int THREADS = 256, int FMT = FSR1_FORMAT_RGBA16F>
 __device__ __forceinline__ void easu_h_stage(const EasuHLds& l, const ImageView& in, const char* in_frame, int fx0, int fy0, int fw_rt, int fh_rt, int tid) {
   const int fw = FW ? FW : fw_rt, fh = FH ? FH : fh_rt;
   const int n = fw * fh - 1;  // the bottom-right corner texel is touched by no 12-tap window (no (2, 2) tap)
@@ -166,22 +223,24 @@ __device__ __forceinline__ void easu_h_stage(const EasuHLds& l, const ImageView&
     const char* const base = in_frame + (long long)gy0 * in.pitch;
     const uint32_t pitch = (uint32_t)in.pitch;
     const half_t hlf = (half_t)0.5f;
+    typedef TexelH<FMT> tex;
+    constexpr uint32_t kPx = (uint32_t)sizeof(typename tex::T);
     auto stage = [&](int i, uint32_t off) {
-      const half4_t c = *reinterpret_cast<const half4_t*>(base + (size_t)off);
+      const half4_t c = tex::load(*reinterpret_cast<const typename tex::T*>(base + (size_t)off));
       l.tex1[i] = half4_t{c.x, c.y, c.z, (half_t)(c.z * hlf + (c.x * hlf + c.y))};  // :535-538
     };
     if (fx0 >= 0 && fy0 >= 0 && fx0 + fw <= in.width && fy0 + fh <= in.height) {  // wave-uniform: nothing to clamp
-      const uint32_t x_off = (uint32_t)fx0 * 8u;
+      const uint32_t x_off = (uint32_t)fx0 * kPx;
       for (int i = tid; i < n; i += THREADS) {
         const int ly = row_of(i);
-        stage(i, (uint32_t)ly * pitch + (uint32_t)(i - ly * fw) * 8u + x_off);
+        stage(i, (uint32_t)ly * pitch + (uint32_t)(i - ly * fw) * kPx + x_off);
       }
     } else {
       for (int i = tid; i < n; i += THREADS) {
         const int ly = row_of(i);
         const int gy = min(max(fy0 + ly, 0), in.height - 1);
         const int gx = min(max(fx0 + (i - ly * fw), 0), in.width - 1);
-        stage(i, (uint32_t)(gy - gy0) * pitch + (uint32_t)gx * 8u);
+        stage(i, (uint32_t)(gy - gy0) * pitch + (uint32_t)gx * kPx);
       }
     }
   }
@@ -262,7 +321,6 @@ __device__ __forceinline__ half2_t prx_med_rcp2(half2_t a) {
 // One FsrRcasHx2 evaluation from its taps (b above, d left, e centre, f right, h below; each a pair of pixels per
 // channel).  `sharp1` = AH2_AU1(con.y).x, the packed half of con[1] (:857).  Returns the pair of sharpened pixels
 // (alpha is the caller's: 1 or the centre tap's, :905-907).
-struct rgbh2_t { half2_t r, g, b; };
 __device__ __forceinline__ rgbh2_t rcas_pixel_h2(half2_t bR, half2_t bG, half2_t bB, half2_t dR, half2_t dG, half2_t dB, half2_t eR, half2_t eG,
                                                  half2_t eB, half2_t fR, half2_t fG, half2_t fB, half2_t hR, half2_t hG, half2_t hB, half_t sharp1,
                                                  uint32_t flags) {

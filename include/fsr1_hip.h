@@ -64,7 +64,16 @@ typedef enum fsr1_format {
    * conversions, which the reference leaves to the API, are pinned here to the D3D11 functional-spec rules:
    *   load  : code / (2^n - 1), correctly rounded to binary32
    *   store : (uint) fma(clamp(x, 0, 1), 2^n - 1, 0.5) — one rounding, then truncation; NaN stores 0
-   * Arithmetic between load and store is the F (binary32) path. */
+   * Arithmetic between load and store is the F (binary32) path — or, with FSR1_FLAG_MATH_PACKED_FP16, the H path (FsrEasuH /
+   * FsrRcasH over these formats is the permutation the reference ships), between these conversions:
+   *   load  : the binary32 load above, rounded once more to binary16, round-to-nearest-even — what a UNORM view read as AH4
+   *           delivers, and what the CPU-evaluated reference does to its binary32 input (float16_t(x), RTNE).  The double
+   *           rounding is harmless: for every one of the 256 + 1024 + 4 codes it equals RTNE of the exact quotient code / (2^n - 1)
+   *           (checked exhaustively on the CPU; 0 codes differ)
+   *   store : the binary16 result widened to binary32 (exact), then the store above
+   * store(load(code)) == code for every code.  Alpha is the maximum code unless FSR1_FLAG_RCAS_PASSTHROUGH_ALPHA; EASU writes
+   * alpha = 1.  The fused launch passes every EASU result through store and load before RCAS reads it, so it stays bit-identical
+   * to the two dispatches with an intermediary of out's format.  in->format == out->format, as for F. */
   FSR1_FORMAT_RGBA8_UNORM = 2,        /* 4 B/pixel: R bits 0-7, G 8-15, B 16-23, A 24-31 */
   FSR1_FORMAT_R10G10B10A2_UNORM = 3   /* 4 B/pixel: R bits 0-9, G 10-19, B 20-29, A 30-31 */
 } fsr1_format;
@@ -101,7 +110,8 @@ enum {
    * EXACT: fp32 arithmetic in the reference's exact operation order, no contraction, IEEE
    * division — bit-identical (fp32) to the CPU-evaluated FsrEasuF / FsrRcasF.
    * PACKED_FP16: the FsrEasuH / FsrRcasH entry points — packed binary16 arithmetic
-   * (v_pk_*_f16), parity class "H" (vs the reference's CPU-evaluated H path). */
+   * (v_pk_*_f16), parity class "H" (vs the reference's CPU-evaluated H path).  Images: RGBA16F, RGBA8_UNORM or
+   * R10G10B10A2_UNORM (not RGBA32F); no colour stages, no row bands. */
   FSR1_FLAG_MATH_EXACT = 1u << 4,
   FSR1_FLAG_MATH_PACKED_FP16 = 1u << 5,
   /* STRICT ("F-strict", round 6): EASU's stored image is BIT-IDENTICAL to FSR1_FLAG_MATH_EXACT's — i.e. to the CPU-evaluated
@@ -275,7 +285,8 @@ typedef struct fsr1_params {
                                           up — round 5: 720p -> 1440p 50.9 vs 47.0 us, sixteen 8K frames 5.45 vs 5.24 ms, one 4K
                                           frame the other way, 93.7 vs 95.6) — and only where the fused tile fits a CU's LDS (up to about 1.9x
                                           minification; beyond that auto keeps the two dispatches); with intermediary == NULL
-                                          it is the fused launch */
+                                          it is the fused launch.  The packed-fp16 thresholds were measured on RGBA16F images;
+                                          RGBA8_UNORM / R10G10B10A2_UNORM images reuse them, unmeasured for 32 bpp */
   uint32_t flags;                      /* FSR1_FLAG_MATH_*, FSR1_FLAG_RCAS_DENOISE / _PASSTHROUGH_ALPHA, FSR1_FLAG_OUTPUT_* (of the pass that writes `out`) */
 } fsr1_params;
 
