@@ -25,6 +25,7 @@ FLAG_RCAS_PASSTHROUGH_ALPHA = 1 << 2
 FLAG_MATH_EXACT = 1 << 4
 FLAG_MATH_PACKED_FP16 = 1 << 5
 FLAG_MATH_STRICT = 1 << 6
+FLAG_COLOR_STAGES_H = 1 << 7  # with FLAG_MATH_PACKED_FP16: fused colour stages run in class H too (otherwise refused)
 FLAG_NO_FAST_PATHS = 1 << 8
 FLAG_OUTPUT_STREAMING = 1 << 9
 FLAG_OUTPUT_CACHED = 1 << 10
@@ -148,7 +149,10 @@ def _con(c, n):
 # --------------------------------------------------------------------------------------------------
 class ColorStages:
     """fsr1_color_stages: which of FsrSrtmF / FsrLfgaF / FsrSrtmInvF / FsrTepdC8F|C10F run, and their inputs
-    (ffx_fsr1.h:986-1199).  `noise` is a CUDA tensor (tiled grain / dither texture, (S,h,w,4) or (h,w,4))."""
+    (ffx_fsr1.h:986-1199).  `noise` is a CUDA tensor (tiled grain / dither texture, (S,h,w,4) or (h,w,4)).
+    With FLAG_MATH_PACKED_FP16 | FLAG_COLOR_STAGES_H the passes run the half-precision forms (FsrSrtmH ...): easu, rcas and
+    Pipeline.upscale as two dispatches or EASU only (FSR_Filter.Upscale adds the second bit itself; color needs only the first); the
+    fused launch (easu_rcas_fused, fused = 1) refuses packed fp16 with stages."""
 
     def __init__(self, stages, grain_amount=0.0, grain_bias=0.0, frame=0, noise=None, noise_offset=(0, 0)):
         self.stages, self.grain_amount, self.grain_bias, self.frame = int(stages), float(grain_amount), float(grain_bias), int(frame)
@@ -276,7 +280,8 @@ def easu_rcas_fused(src, dst, easu_con=None, rcas_con=None, sharpness=0.25, flag
 
 
 def color(src, dst, stages, flags=0, stream=None):
-    """dst = stages(src): the stand-alone colour pass (FsrSrtmF -> FsrLfgaF -> FsrSrtmInvF -> FsrTepdC8F|C10F)."""
+    """dst = stages(src): the stand-alone colour pass (FsrSrtmF -> FsrLfgaF -> FsrSrtmInvF -> FsrTepdC8F|C10F).
+    flags = FLAG_MATH_PACKED_FP16: the reference's half-precision stages (class H) between any two of RGBA16F, RGBA8 and R10G10B10A2."""
     i, o = image_of(src), image_of(dst)
     sp, _keep = _stages(stages)
     _lib.check(_lib.load().fsr1_color_dispatch(ctypes.byref(i), ctypes.byref(o), sp, flags, _stream_ptr(stream)))
@@ -351,7 +356,8 @@ class FSR_Filter:
         hdr = self._hdr if hdr is None else hdr
         p = fsr1_params(float(pState.renderWidth), float(pState.renderHeight), int(bool(pState.bUseRcas)),
                         float(pState.rcasAttenuation), int(bool(hdr)),
-                        (2 if self.fused == "auto" else int(bool(self.fused))) if pState.bUseRcas else 0, self._flags)
+                        (2 if self.fused == "auto" else int(bool(self.fused))) if pState.bUseRcas else 0,
+                        self._flags | (FLAG_COLOR_STAGES_H if stages is not None and self._flags & FLAG_MATH_PACKED_FP16 else 0))
         i, o = image_of(self._input), image_of(self._output)
         if (o.width, o.height) != (displayWidth, displayHeight):
             raise Fsr1Error("display size changed: call OnCreateWindowSizeDependentResources again")

@@ -33,15 +33,16 @@ int fused_s2_run_steps(int width, int height, int frames, int cus, int wgs_per_c
 hipError_t fused_s2_h_launch(const FusedArgs& a, int fmt, hipStream_t stream);
 size_t fused_s2_h_lds_bytes();
 size_t fused_h_lds_bytes(int fp_w, int fp_h);
-hipError_t easu_h_launch(const EasuArgs& a, int fmt, bool s2, hipStream_t stream);
+hipError_t easu_h_launch(const EasuArgs& a, int fmt, int fout, bool s2, hipStream_t stream);
 hipError_t easu_color_launch(const EasuArgs& a, int fin, int fout, bool exact, hipStream_t stream);
 hipError_t rcas_color_launch(const RcasArgs& a, int fin, int fout, bool exact, hipStream_t stream);
 hipError_t fused_color_launch(const FusedArgs& a, int fin, int fout, bool exact, hipStream_t stream);
 hipError_t color_launch(const ColorPassArgs& a, int fin, int fout, bool exact, hipStream_t stream);
-hipError_t color_h_launch(const ColorPassArgs& a, hipStream_t stream);
+hipError_t color_h_launch(const ColorPassArgs& a, int fin, int fout, hipStream_t stream);
+void color_h_geometry(int fin, int fout, int width, int height, int* tiles_x, int* tiles_y);
 void color_geometry(int width, int height, int* tiles_x, int* tiles_y);
-hipError_t rcas_h_launch(const RcasArgs& a, int fmt, hipStream_t stream);
-void rcas_h_geometry(int fmt, int width, int height, int* tiles_x, int* tiles_y);
+hipError_t rcas_h_launch(const RcasArgs& a, int fmt, int fout, hipStream_t stream);
+void rcas_h_geometry(int fmt, int fout, int width, int height, int* tiles_x, int* tiles_y);
 }  // namespace fsr1
 
 using namespace fsr1;
@@ -191,7 +192,7 @@ static int check_grid(const char* who, int tiles_x, int tiles_y, int frames) {
 }
 
 static const uint32_t kKnownFlags = FSR1_FLAG_HDR_SQUARE | FSR1_FLAG_RCAS_DENOISE | FSR1_FLAG_RCAS_PASSTHROUGH_ALPHA |
-                                    FSR1_FLAG_MATH_EXACT | FSR1_FLAG_MATH_PACKED_FP16 | FSR1_FLAG_MATH_STRICT | FSR1_FLAG_NO_FAST_PATHS |
+                                    FSR1_FLAG_MATH_EXACT | FSR1_FLAG_MATH_PACKED_FP16 | FSR1_FLAG_MATH_STRICT | FSR1_FLAG_COLOR_STAGES_H | FSR1_FLAG_NO_FAST_PATHS |
                                     FSR1_FLAG_OUTPUT_STREAMING | FSR1_FLAG_OUTPUT_CACHED | FSR1_FLAG_FRAMES_OVERLAP;
 
 static int check_flags(uint32_t flags) {
@@ -200,6 +201,8 @@ static int check_flags(uint32_t flags) {
     return fail(FSR1_ERR_INVALID_ARGUMENT, "FSR1_FLAG_MATH_EXACT and FSR1_FLAG_MATH_PACKED_FP16 are exclusive");
   if ((flags & FSR1_FLAG_MATH_STRICT) && (flags & (FSR1_FLAG_MATH_EXACT | FSR1_FLAG_MATH_PACKED_FP16)))
     return fail(FSR1_ERR_INVALID_ARGUMENT, "FSR1_FLAG_MATH_STRICT is exclusive with FSR1_FLAG_MATH_EXACT and FSR1_FLAG_MATH_PACKED_FP16");
+  if ((flags & FSR1_FLAG_COLOR_STAGES_H) && !(flags & FSR1_FLAG_MATH_PACKED_FP16))
+    return fail(FSR1_ERR_INVALID_ARGUMENT, "FSR1_FLAG_COLOR_STAGES_H needs FSR1_FLAG_MATH_PACKED_FP16");
   if ((flags & FSR1_FLAG_OUTPUT_STREAMING) && (flags & FSR1_FLAG_OUTPUT_CACHED))
     return fail(FSR1_ERR_INVALID_ARGUMENT, "FSR1_FLAG_OUTPUT_STREAMING and FSR1_FLAG_OUTPUT_CACHED are exclusive");
   return FSR1_OK;
@@ -379,7 +382,10 @@ static int easu_dispatch_impl(const fsr1_image* in, const fsr1_image* out, const
   if (!con) return fail(FSR1_ERR_INVALID_ARGUMENT, "easu: null constants");
   if (a.color.stages ? !color_format_pair_ok(in->format, out->format) : in->format != out->format)
     return fail(FSR1_ERR_UNSUPPORTED, "easu: unsupported input/output format pair %d -> %d", in->format, out->format);
-  if (a.color.stages && (flags & FSR1_FLAG_MATH_PACKED_FP16)) return fail(FSR1_ERR_UNSUPPORTED, "easu: colour stages run with the F (binary32) arithmetic");
+  // packed fp16 with colour stages: the class-H stages when FSR1_FLAG_COLOR_STAGES_H asks for them (for the pairs above among the formats
+  // class H accepts — checked at the launch); the stages' arithmetic is never chosen silently
+  if (a.color.stages && (flags & FSR1_FLAG_MATH_PACKED_FP16) && !(flags & FSR1_FLAG_COLOR_STAGES_H))
+    return fail(FSR1_ERR_UNSUPPORTED, "easu: colour stages run with the F (binary32) arithmetic unless FSR1_FLAG_COLOR_STAGES_H selects the class-H stages");
   if (in->frames != out->frames) return fail(FSR1_ERR_INVALID_ARGUMENT, "easu: frame counts differ (%d vs %d)", in->frames, out->frames);
   if (overlaps(in, a.in, out, a.out)) return fail(FSR1_ERR_INVALID_ARGUMENT, "easu: input and output overlap");
   // F-strict promises EXACT's stored image: where there is no conversion to test against (RGBA32F stores the binary32 result itself)
@@ -419,7 +425,8 @@ static int easu_dispatch_impl(const fsr1_image* in, const fsr1_image* out, const
   // out = 2 * in — takes the variant whose lanes own 2x2 output quads; its tiles are shifted by one pixel, hence one
   // more tile per axis when the size is a multiple of the tile, and the footprint of a tile is 64/2+3 x 16/2+3 texels.
   const bool s2 = con[0] == 0x3f000000u && con[1] == 0x3f000000u && con[2] == 0xbe800000u && con[3] == 0xbe800000u &&
-                  !(flags & FSR1_FLAG_NO_FAST_PATHS) && !a.color.stages && kTileH % 16 == 0 && !((origin_x | origin_y) & 1);
+                  !(flags & FSR1_FLAG_NO_FAST_PATHS) && (!a.color.stages || (flags & FSR1_FLAG_MATH_PACKED_FP16)) && kTileH % 16 == 0 &&
+                  !((origin_x | origin_y) & 1);  // (with colour stages: the H kernels have an exact-2x variant, the F kernels do not)
   // (64 x 32 tiles for whole-image F launches that are large or overlapped: easu_s2_tall_tiles)
   bool tall = s2 && !(flags & (FSR1_FLAG_MATH_PACKED_FP16 | FSR1_FLAG_MATH_EXACT)) && !origin_x && !origin_y &&
               easu_s2_tall_tiles(out->width, out->height, out->frames, (flags & FSR1_FLAG_FRAMES_OVERLAP) != 0, device_cus());
@@ -448,7 +455,7 @@ static int easu_dispatch_impl(const fsr1_image* in, const fsr1_image* out, const
   hipError_t e;
   if (flags & FSR1_FLAG_MATH_PACKED_FP16) {
     if (!packed_format_ok(in->format)) return fail(FSR1_ERR_UNSUPPORTED, "easu: packed-fp16 math needs RGBA16F, RGBA8_UNORM or R10G10B10A2_UNORM images");
-    e = easu_h_launch(a, in->format, s2, static_cast<hipStream_t>(stream));
+    e = easu_h_launch(a, in->format, out->format, s2, static_cast<hipStream_t>(stream));
   } else if (a.color.stages) {
     e = easu_color_launch(a, in->format, out->format, (flags & FSR1_FLAG_MATH_EXACT) != 0, static_cast<hipStream_t>(stream));
   } else {
@@ -498,7 +505,8 @@ static int rcas_dispatch_impl(const fsr1_image* in, const fsr1_image* out, const
   if (!con) return fail(FSR1_ERR_INVALID_ARGUMENT, "rcas: null constants");
   if (a.color.stages ? !color_format_pair_ok(in->format, out->format) : in->format != out->format)
     return fail(FSR1_ERR_UNSUPPORTED, "rcas: unsupported input/output format pair %d -> %d", in->format, out->format);
-  if (a.color.stages && (flags & FSR1_FLAG_MATH_PACKED_FP16)) return fail(FSR1_ERR_UNSUPPORTED, "rcas: colour stages run with the F (binary32) arithmetic");
+  if (a.color.stages && (flags & FSR1_FLAG_MATH_PACKED_FP16) && !(flags & FSR1_FLAG_COLOR_STAGES_H))
+    return fail(FSR1_ERR_UNSUPPORTED, "rcas: colour stages run with the F (binary32) arithmetic unless FSR1_FLAG_COLOR_STAGES_H selects the class-H stages");
   if (in->width != out->width || in->height != out->height || in->frames != out->frames)
     return fail(FSR1_ERR_INVALID_ARGUMENT, "rcas: input %dx%dx%d and output %dx%dx%d extents differ", in->width, in->height,
                 in->frames, out->width, out->height, out->frames);
@@ -520,9 +528,9 @@ static int rcas_dispatch_impl(const fsr1_image* in, const fsr1_image* out, const
   hipError_t e;
   if (flags & FSR1_FLAG_MATH_PACKED_FP16) {
     if (!packed_format_ok(in->format)) return fail(FSR1_ERR_UNSUPPORTED, "rcas: packed-fp16 math needs RGBA16F, RGBA8_UNORM or R10G10B10A2_UNORM images");
-    rcas_h_geometry(in->format, out->width, out->height, &a.tiles_x, &a.tiles_y);  // the H kernels' own strip shapes
+    rcas_h_geometry(in->format, out->format, out->width, out->height, &a.tiles_x, &a.tiles_y);  // the H kernels' own strip shapes
     if ((rc = check_grid("rcas", a.tiles_x, a.tiles_y, a.frames))) return rc;
-    e = rcas_h_launch(a, in->format, static_cast<hipStream_t>(stream));
+    e = rcas_h_launch(a, in->format, out->format, static_cast<hipStream_t>(stream));
   } else if (a.color.stages) {
     e = rcas_color_launch(a, in->format, out->format, (flags & FSR1_FLAG_MATH_EXACT) != 0, static_cast<hipStream_t>(stream));
   } else {
@@ -579,8 +587,11 @@ static int fused_dispatch_impl(const fsr1_image* in, const fsr1_image* out, cons
   if ((flags & FSR1_FLAG_MATH_STRICT) && (in->format == FSR1_FORMAT_RGBA32F || a.color.stages))
     flags = (flags & ~(uint32_t)FSR1_FLAG_MATH_STRICT) | FSR1_FLAG_MATH_EXACT;
   const bool packed = (flags & FSR1_FLAG_MATH_PACKED_FP16) != 0;
-  if (packed && (!packed_format_ok(in->format) || a.color.stages))
-    return fail(FSR1_ERR_UNSUPPORTED, "fused: packed-fp16 math needs RGBA16F, RGBA8_UNORM or R10G10B10A2_UNORM images and runs without colour stages");
+  if (packed && !packed_format_ok(in->format))
+    return fail(FSR1_ERR_UNSUPPORTED, "fused: packed-fp16 math needs RGBA16F, RGBA8_UNORM or R10G10B10A2_UNORM images");
+  if (packed && a.color.stages)
+    return fail(FSR1_ERR_UNSUPPORTED, "fused: the fused launches of packed-fp16 math run without colour stages; the EASU and RCAS dispatches take them "
+                                      "(fsr1_easu_dispatch_ex + fsr1_rcas_dispatch_ex, or fsr1_upscale_ex with fused = 0 / 2 and an intermediary)");
   memcpy(a.easu_con, easu_con, sizeof a.easu_con);
   memcpy(a.rcas_con, rcas_con, sizeof a.rcas_con);
   float sx, sy, bx, by;
@@ -632,8 +643,8 @@ int fsr1_color_dispatch(const fsr1_image* in, const fsr1_image* out, const fsr1_
   ColorPassArgs a;
   a.xcd_shift = device_xcd_shift();
   int rc;
-  if (flags & ~(uint32_t)(FSR1_FLAG_MATH_EXACT | FSR1_FLAG_MATH_PACKED_FP16))
-    return fail(FSR1_ERR_INVALID_ARGUMENT, "color: flags may only hold FSR1_FLAG_MATH_EXACT or FSR1_FLAG_MATH_PACKED_FP16");
+  if (flags & ~(uint32_t)(FSR1_FLAG_MATH_EXACT | FSR1_FLAG_MATH_PACKED_FP16 | FSR1_FLAG_COLOR_STAGES_H))
+    return fail(FSR1_ERR_INVALID_ARGUMENT, "color: flags may only hold FSR1_FLAG_MATH_EXACT or FSR1_FLAG_MATH_PACKED_FP16 (+ FSR1_FLAG_COLOR_STAGES_H)");
   if ((rc = check_flags(flags))) return rc;
   if ((rc = check_image(in, "color input", &a.in))) return rc;
   if ((rc = check_image(out, "color output", &a.out))) return rc;
@@ -644,14 +655,16 @@ int fsr1_color_dispatch(const fsr1_image* in, const fsr1_image* out, const fsr1_
   if (overlaps(in, a.in, out, a.out) &&
       !(in->data == out->data && in->format == out->format && a.in.pitch == a.out.pitch && a.in.frame_stride == a.out.frame_stride))
     return fail(FSR1_ERR_INVALID_ARGUMENT, "color: input and output overlap without being the same image");
-  color_geometry(out->width, out->height, &a.tiles_x, &a.tiles_y);
+  const bool packed = (flags & FSR1_FLAG_MATH_PACKED_FP16) != 0;
+  if (packed && !(packed_format_ok(in->format) && packed_format_ok(out->format)))
+    return fail(FSR1_ERR_UNSUPPORTED, "color: packed-fp16 math needs RGBA16F, RGBA8_UNORM or R10G10B10A2_UNORM images");
+  if (packed) color_h_geometry(in->format, out->format, out->width, out->height, &a.tiles_x, &a.tiles_y);  // two or four pixels per lane
+  else color_geometry(out->width, out->height, &a.tiles_x, &a.tiles_y);
   a.frames = out->frames;
   if ((rc = check_grid("color", a.tiles_x, a.tiles_y, a.frames))) return rc;
   hipError_t e;
-  if (flags & FSR1_FLAG_MATH_PACKED_FP16) {
-    if (in->format != FSR1_FORMAT_RGBA16F || out->format != FSR1_FORMAT_RGBA16F)
-      return fail(FSR1_ERR_UNSUPPORTED, "color: packed-fp16 math needs RGBA16F images");
-    e = color_h_launch(a, static_cast<hipStream_t>(stream));
+  if (packed) {
+    e = color_h_launch(a, in->format, out->format, static_cast<hipStream_t>(stream));
   } else {
     e = color_launch(a, in->format, out->format, (flags & FSR1_FLAG_MATH_EXACT) != 0, static_cast<hipStream_t>(stream));
   }
@@ -689,15 +702,21 @@ static int upscale_decide(const char* who, const fsr1_image* in, bool have_inter
                 (double)p->render_height, in->width, in->height);
   int rc;
   if ((rc = check_flags(p->flags))) return rc;
-  plan->math = p->flags & (FSR1_FLAG_MATH_EXACT | FSR1_FLAG_MATH_PACKED_FP16 | FSR1_FLAG_MATH_STRICT | FSR1_FLAG_NO_FAST_PATHS);
+  plan->math = p->flags & (FSR1_FLAG_MATH_EXACT | FSR1_FLAG_MATH_PACKED_FP16 | FSR1_FLAG_MATH_STRICT | FSR1_FLAG_COLOR_STAGES_H | FSR1_FLAG_NO_FAST_PATHS);
   const uint32_t rcas_opts = p->flags & (FSR1_FLAG_RCAS_DENOISE | FSR1_FLAG_RCAS_PASSTHROUGH_ALPHA);
   plan->out_policy = p->flags & (FSR1_FLAG_OUTPUT_STREAMING | FSR1_FLAG_OUTPUT_CACHED);  // of the pass that writes `out`
   const uint32_t overlap = p->flags & FSR1_FLAG_FRAMES_OVERLAP;  // a scheduling hint: travels with the math bits to every pass
   if (p->flags & ~(plan->math | rcas_opts | plan->out_policy | overlap))
     return fail(FSR1_ERR_INVALID_ARGUMENT, "%s: params.flags may only hold MATH_*, RCAS_*, OUTPUT_* and FRAMES_OVERLAP bits", who);
   plan->math |= overlap;
-  if ((plan->math & FSR1_FLAG_MATH_PACKED_FP16) && (!packed_format_ok(in->format) || out->format != in->format || have_stages))
-    return fail(FSR1_ERR_UNSUPPORTED, "%s: packed-fp16 math needs RGBA16F, RGBA8_UNORM or R10G10B10A2_UNORM images of one format and runs without colour stages", who);
+  // packed fp16: one class-H format throughout — with colour stages (FSR1_FLAG_COLOR_STAGES_H: without it they stay refused) the output may
+  // also be a TEPD target of an RGBA16F input
+  if ((plan->math & FSR1_FLAG_MATH_PACKED_FP16) && have_stages && !(plan->math & FSR1_FLAG_COLOR_STAGES_H))
+    return fail(FSR1_ERR_UNSUPPORTED, "%s: packed-fp16 math runs without colour stages unless FSR1_FLAG_COLOR_STAGES_H selects the class-H stages", who);
+  if ((plan->math & FSR1_FLAG_MATH_PACKED_FP16) &&
+      (!packed_format_ok(in->format) || !packed_format_ok(out->format) || (have_stages ? !color_format_pair_ok(in->format, out->format) : out->format != in->format)))
+    return fail(FSR1_ERR_UNSUPPORTED, "%s: packed-fp16 math needs RGBA16F, RGBA8_UNORM or R10G10B10A2_UNORM images, of one format or (with colour stages) "
+                                      "RGBA16F in and a 32 bpp UNORM format out", who);
   // :106 — viewport == input resource size == (renderWidth, renderHeight); output = display size
   FsrEasuCon(plan->easu_con, plan->easu_con + 4, plan->easu_con + 8, plan->easu_con + 12, p->render_width, p->render_height, p->render_width,
              p->render_height, (float)out->width, (float)out->height);
@@ -720,7 +739,12 @@ static int upscale_decide(const char* who, const fsr1_image* in, bool have_inter
   FsrRcasCon(plan->rcas_con, p->rcas_attenuation);  // :124
   plan->rcas_flags = plan->math | rcas_opts | plan->out_policy | (p->hdr ? FSR1_FLAG_HDR_SQUARE : 0u);  // :125 Sample.x = hdr
   if (p->fused != 0 && p->fused != 1 && p->fused != 2) return fail(FSR1_ERR_INVALID_ARGUMENT, "%s: params.fused must be 0, 1 or 2 (auto)", who);
-  const bool fused = p->fused == 1 || (p->fused == 2 && auto_takes_fused(in, have_intermediary, out, plan->easu_con, plan->math, have_stages));
+  // packed fp16 with colour stages: the two fused H launches have no stages (fused_dispatch_impl refuses them), so `auto` always plans the
+  // two dispatches — and where it could only mean the fused launch (no intermediary) the refusal is made here, not by a launch
+  if (packed && have_stages && (p->fused == 1 || !have_intermediary))
+    return fail(FSR1_ERR_UNSUPPORTED, "%s: the fused launch of packed-fp16 math runs without colour stages; pass an intermediary and fused = 0 or 2", who);
+  const bool fused = p->fused == 1 || (p->fused == 2 && !(packed && have_stages) &&
+                                       auto_takes_fused(in, have_intermediary, out, plan->easu_con, plan->math, have_stages));
   if (!fused && !have_intermediary) return fail(FSR1_ERR_INVALID_ARGUMENT, "%s: two-pass EASU+RCAS needs an intermediary image", who);
   if (fused) {  // the fused launch's own LDS bound (fused_dispatch_impl)
     const int ffw = footprint_extent(out->width, kTileW, 1, sx, bx), ffh = footprint_extent(out->height, kFusedTileH, 1, sy, by);
@@ -880,8 +904,10 @@ int fsr1_pipeline_upscale(fsr1_pipeline* p, const fsr1_image* in, const fsr1_ima
   // profiles/ab_r05/r5c8_batch_vs_frames.log: 111.6 Gpix/s as launch pairs over three streams, 118.5 frame by frame).  Frame f of the batch
   // runs on slot (next_slot + f) mod N; the frames are the same kernels on the same values as in one launch: bit-identical
   // (tests/test_gpu_pipeline.py).  8K frames (265 MB each) and fused launches keep the single launch.
+  // the intermediary has out's format — in's under packed fp16, whose EASU keeps its input's format (they differ only with colour stages)
+  const int mid_format = (plan.math & FSR1_FLAG_MATH_PACKED_FP16) ? in->format : out->format;
   if (plan.pipeline == 0 && out->frames > 1 && p->n > 1 &&
-      (size_t)out->width * pixel_bytes(out->format) * (size_t)out->height * (size_t)p->n <= infinity_cache_bytes()) {
+      (size_t)out->width * pixel_bytes(mid_format) * (size_t)out->height * (size_t)p->n <= infinity_cache_bytes()) {
     ImageView vi, vo;
     if (int rc = check_image(in, "pipeline_upscale input", &vi)) return rc;
     if (int rc = check_image(out, "pipeline_upscale output", &vo)) return rc;
@@ -916,10 +942,10 @@ int fsr1_pipeline_upscale(fsr1_pipeline* p, const fsr1_image* in, const fsr1_ima
   const int slot = p->next;
   fsr1_image mid_img;
   const fsr1_image* mid_p = nullptr;
-  if (plan.pipeline == 0) {  // two dispatches: this slot's own intermediary, out's format and extent
-    const size_t need = (size_t)out->width * pixel_bytes(out->format) * (size_t)out->height * (size_t)out->frames;
+  if (plan.pipeline == 0) {  // two dispatches: this slot's own intermediary, out's extent
+    const size_t need = (size_t)out->width * pixel_bytes(mid_format) * (size_t)out->height * (size_t)out->frames;
     if (int rc = pipeline_grow(p, slot, need, "pipeline_upscale")) return rc;
-    mid_img = fsr1_image{p->mid[slot], out->width, out->height, out->format, out->frames, 0, 0};
+    mid_img = fsr1_image{p->mid[slot], out->width, out->height, mid_format, out->frames, 0, 0};
     mid_p = &mid_img;
   }
   // (the plan is re-derived by fsr1_upscale_ex from the same arguments: `auto` with an intermediary on offer decides as it did above)

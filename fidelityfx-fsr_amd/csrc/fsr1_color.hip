@@ -7,6 +7,7 @@
 // row loads are issued before the first use; the four waves of a workgroup stack vertically (128 x 32 tile).
 // The noise tile (a few KiB) stays in L2.
 #include "fsr1_device_color.hpp"
+#include "fsr1_device_half.hpp"
 #include "fsr1_device.h"
 
 namespace fsr1 {
@@ -70,38 +71,10 @@ __global__ void __launch_bounds__(kThreads) color_kernel(const ColorPassArgs a) 
   }
 }
 
-// ---- packed binary16 arithmetic: FsrSrtmHx2 / FsrLfgaHx2 / FsrSrtmInvHx2 / FsrTepdC8Hx2 | C10Hx2 with FsrTepdDitHx2's
-//      per-lane formula (ffx_fsr1.h:1017-1024, :1048-1056, :1124-1198).  A lane's two adjacent pixels are the two halves
-//      of every AH2; each reference operation is one native binary16 operation (contraction off), so the result is
-//      bit-identical to the CPU-evaluated H path (parity class "H").  RGBA16F in and out. ----
-__device__ __forceinline__ half2_t c_h2(half_t a, half_t b) { return half2_t{a, b}; }
-__device__ __forceinline__ half2_t c_h2s(half_t a) { return half2_t{a, a}; }
-__device__ __forceinline__ half2_t c_max2(half2_t a, half2_t b) { return __builtin_elementwise_max(a, b); }
-__device__ __forceinline__ half2_t c_min2(half2_t a, half2_t b) { return __builtin_elementwise_min(a, b); }
-__device__ __forceinline__ half2_t c_sat2(half2_t a) { return c_min2(c_max2(a, c_h2s((half_t)0.0f)), c_h2s((half_t)1.0f)); }
-__device__ __forceinline__ half2_t c_rcp2(half2_t a) { return half2_t{half_rcp(a.x), half_rcp(a.y)}; }  // ARcpH2: correctly rounded 1/x
-// correctly rounded binary16 sqrt: the binary32 sqrt (correctly rounded) narrowed RTNE is exact-rounding because 24 >= 2*11+2
-__device__ __forceinline__ half2_t c_sqrt2(half2_t a) { return half2_t{(half_t)sqrtf((float)a.x), (half_t)sqrtf((float)a.y)}; }
-__device__ __forceinline__ half2_t c_floor2(half2_t a) { return half2_t{(half_t)__builtin_floorf16(a.x), (half_t)__builtin_floorf16(a.y)}; }
-// ffx_a.h:1815 APrxMedRcpH2
-__device__ __forceinline__ half2_t APrxMedRcpH2(half2_t a) {
-  typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-  const u16x2 ai = __builtin_bit_cast(u16x2, a);
-  const u16x2 bi = {(unsigned short)(0x778du - ai.x), (unsigned short)(0x778du - ai.y)};
-  const half2_t b = __builtin_bit_cast(half2_t, bi);
-  return b * (-b * a + c_h2s((half_t)2.0f));
-}
-__device__ __forceinline__ half2_t AGtZeroH2(half2_t m) { return c_sat2(m * c_h2s((half_t)__builtin_inff())); }  // ffx_a.h:1525
-__device__ __forceinline__ half2_t FsrTepdCHx2(half2_t c, half2_t dit, half_t k, half_t rk) {  // :1153-1198, one channel
-  half2_t n = c_sqrt2(c);
-  n = c_floor2(n * c_h2s(k)) * c_h2s(rk);
-  const half2_t a = n * n;
-  half2_t b = n + c_h2s(rk);
-  b = b * b;
-  const half2_t r = (c - b) * APrxMedRcpH2(a - b);
-  return c_sat2(n + AGtZeroH2(dit - r) * c_h2s(rk));
-}
-
+// ---- packed binary16 arithmetic (parity class "H"): color_prologue_h2 / color_epilogue_h2 of fsr1_device_color_half.hpp — the
+//      reference's Hx2 stages, a lane's adjacent pixels in the two halves of every AH2, bit-identical to the CPU-evaluated H path.
+//      Loads and stores follow TexelH (fsr1_device_half.hpp), alpha passes through it unchanged. ----
+// RGBA16F in and out: two pixels per lane, one 16-byte access each way per row.
 __global__ void __launch_bounds__(kThreads) color_h_kernel(const ColorPassArgs a) {
   const int tiles_per_frame = a.tiles_x * a.tiles_y;
   const int t = xcd_swizzle(blockIdx.x, tiles_per_frame * a.frames, a.xcd_shift);
@@ -116,11 +89,6 @@ __global__ void __launch_bounds__(kThreads) color_h_kernel(const ColorPassArgs a
   const char* src = a.in.base + (long long)frame * a.in.frame_stride + (size_t)x * sizeof(half4_t);
   char* dst = a.out.base + (long long)frame * a.out.frame_stride + (size_t)x * sizeof(half4_t);
   struct __attribute__((aligned(8))) px2_t { half4_t p[2]; };
-  const uint32_t st = a.color.stages;
-  const half_t one = (half_t)1.0f;
-  const half2_t amount = c_h2s((half_t)a.color.amount), bias = c_h2s((half_t)a.color.bias);
-  const bool c8 = (st & FSR1_COLOR_TEPD_C8) != 0;
-  const half_t k = c8 ? (half_t)255.0f : (half_t)1023.0f, rk = c8 ? (half_t)(1.0 / 255.0) : (half_t)(1.0 / 1023.0);
 #pragma unroll 1
   for (int r = 0; r < kColorRowsPerWave; ++r) {
     const int y = y0 + r;
@@ -128,42 +96,114 @@ __global__ void __launch_bounds__(kThreads) color_h_kernel(const ColorPassArgs a
     px2_t q;
     if (pair) q = *reinterpret_cast<const px2_t*>(src + (long long)y * a.in.pitch);
     else { q.p[0] = *reinterpret_cast<const half4_t*>(src + (long long)y * a.in.pitch); q.p[1] = q.p[0]; }
-    half2_t cR = c_h2(q.p[0].x, q.p[1].x), cG = c_h2(q.p[0].y, q.p[1].y), cB = c_h2(q.p[0].z, q.p[1].z);
-    float4_t n0 = {0.f, 0.f, 0.f, 0.f}, n1 = n0;
-    if (st & kColorNeedsNoise) { n0 = noise_fetch(a.color.noise, (uint32_t)x, (uint32_t)y); n1 = noise_fetch(a.color.noise, (uint32_t)x + 1u, (uint32_t)y); }
-    if (st & FSR1_COLOR_SRTM) {  // :1052-1053
-      const half2_t rcp = c_rcp2(c_max2(cR, c_max2(cG, cB)) + c_h2s(one));
-      cR = cR * rcp; cG = cG * rcp; cB = cB * rcp;
-    }
-    if (st & FSR1_COLOR_LFGA) {  // :1022-1023
-      const half2_t tR = c_h2((half_t)n0.x, (half_t)n1.x) + bias, tG = c_h2((half_t)n0.y, (half_t)n1.y) + bias, tB = c_h2((half_t)n0.z, (half_t)n1.z) + bias;
-      cR = cR + (tR * amount) * c_min2(c_h2s(one) - cR, cR);
-      cG = cG + (tG * amount) * c_min2(c_h2s(one) - cG, cG);
-      cB = cB + (tB * amount) * c_min2(c_h2s(one) - cB, cB);
-    }
-    if (st & FSR1_COLOR_SRTM_INV) {  // :1054-1055
-      const half2_t rcp = c_rcp2(c_max2(c_h2s((half_t)(1.0 / 32768.0)), c_h2s(one) - c_max2(cR, c_max2(cG, cB))));
-      cR = cR * rcp; cG = cG * rcp; cB = cB * rcp;
-    }
-    if (st & (FSR1_COLOR_TEPD_C8 | FSR1_COLOR_TEPD_C10)) {
-      // :1153-1160 FsrTepdDitHx2 is FsrTepdDitH per lane: binary32 arithmetic, narrowed once
-      const half2_t dit = (st & FSR1_COLOR_DITHER_FROM_NOISE)
-                              ? c_sat2(c_h2((half_t)n0.w, (half_t)n1.w))
-                              : c_h2((half_t)FsrTepdDitF((uint32_t)x, (uint32_t)y, a.color.frame), (half_t)FsrTepdDitF((uint32_t)x + 1u, (uint32_t)y, a.color.frame));
-      cR = FsrTepdCHx2(cR, dit, k, rk); cG = FsrTepdCHx2(cG, dit, k, rk); cB = FsrTepdCHx2(cB, dit, k, rk);
-    }
+    rgbh2_t c = {c_h2(q.p[0].x, q.p[1].x), c_h2(q.p[0].y, q.p[1].y), c_h2(q.p[0].z, q.p[1].z)};
+    color_prologue_h2(a.color, c);
+    color_epilogue_h2(a.color, (uint32_t)x, (uint32_t)x + 1u, (uint32_t)y, c);
     px2_t o;
-    o.p[0] = half4_t{cR.x, cG.x, cB.x, q.p[0].w};
-    o.p[1] = half4_t{cR.y, cG.y, cB.y, q.p[1].w};
+    o.p[0] = half4_t{c.r.x, c.g.x, c.b.x, q.p[0].w};
+    o.p[1] = half4_t{c.r.y, c.g.y, c.b.y, q.p[1].w};
     char* p = dst + (long long)y * a.out.pitch;
     if (pair) *reinterpret_cast<px2_t*>(p) = o;
     else *reinterpret_cast<half4_t*>(p) = o.p[0];
   }
 }
 
-hipError_t color_h_launch(const ColorPassArgs& a, hipStream_t stream) {
+// A 32 bpp UNORM format on either side: FOUR adjacent pixels per lane, so that the 4-byte side moves as one 16-byte access per
+// lane-row (an RGBA16F side as two, 32 contiguous bytes) — the access width this chip moves at full rate (fsr1_rcas_h.hip).  A wave
+// covers 256 columns x 8 rows, the four waves of a workgroup stack vertically (256 x 32 tile).  A lane reads its four texels before it
+// writes them, so the pass runs in place when the formats match.
+constexpr int kColorH4Cols = 4 * 64;
+
+// n (1 .. 4) adjacent texels of a row; rows are only texel-aligned.  A ragged right edge goes texel by texel.
+template <int FMT>
+struct QuadH {
+  typedef typename TexelH<FMT>::T tex_t;
+  struct __attribute__((aligned(sizeof(tex_t) < 8 ? 4 : 8))) T { tex_t v[4]; };
+  static __device__ __forceinline__ void load(const char* p, int n, half4_t t[4]) {
+    T q;
+    if (n == 4) {
+      q = *reinterpret_cast<const T*>(p);
+    } else {
+      const tex_t* const px = reinterpret_cast<const tex_t*>(p);
+      q.v[0] = px[0];
+      q.v[1] = n > 1 ? px[1] : q.v[0];
+      q.v[2] = n > 2 ? px[2] : q.v[0];
+      q.v[3] = q.v[0];
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) t[i] = TexelH<FMT>::load(q.v[i]);
+  }
+  static __device__ __forceinline__ void store(char* p, int n, const half4_t t[4]) {
+    T q;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) q.v[i] = TexelH<FMT>::store(t[i]);
+    if (n == 4) {
+      *reinterpret_cast<T*>(p) = q;
+    } else {
+      tex_t* const px = reinterpret_cast<tex_t*>(p);
+      px[0] = q.v[0];
+      if (n > 1) px[1] = q.v[1];
+      if (n > 2) px[2] = q.v[2];
+    }
+  }
+};
+
+template <int FIN, int FOUT>
+__global__ void __launch_bounds__(kThreads) color_h4_kernel(const ColorPassArgs a) {
+  const int tiles_per_frame = a.tiles_x * a.tiles_y;
+  const int t = xcd_swizzle(blockIdx.x, tiles_per_frame * a.frames, a.xcd_shift);
+  const int frame = t / tiles_per_frame;
+  const int tf = t - frame * tiles_per_frame;
+  const int ty = tf / a.tiles_x, tx = tf - ty * a.tiles_x;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int x = tx * kColorH4Cols + 4 * lane, y0 = ty * kColorRows + wave * kColorRowsPerWave;
+  const int W = a.in.width, H = a.in.height;
+  if (x >= W || y0 >= H) return;
+  const int n = min(W - x, 4);  // this lane's pixels inside the image
+  const char* src = a.in.base + (long long)frame * a.in.frame_stride + (size_t)x * sizeof(typename TexelH<FIN>::T);
+  char* dst = a.out.base + (long long)frame * a.out.frame_stride + (size_t)x * sizeof(typename TexelH<FOUT>::T);
+#pragma unroll 1
+  for (int r = 0; r < kColorRowsPerWave; ++r) {
+    const int y = y0 + r;
+    if (y >= H) break;
+    half4_t q[4];
+    QuadH<FIN>::load(src + (long long)y * a.in.pitch, n, q);
+    rgbh2_t lo = {c_h2(q[0].x, q[1].x), c_h2(q[0].y, q[1].y), c_h2(q[0].z, q[1].z)};
+    rgbh2_t hi = {c_h2(q[2].x, q[3].x), c_h2(q[2].y, q[3].y), c_h2(q[2].z, q[3].z)};
+    color_prologue_h2(a.color, lo);
+    color_prologue_h2(a.color, hi);
+    // (the noise tile wraps, so the positions of a ragged lane's missing pixels are fetched harmlessly)
+    color_epilogue_h2(a.color, (uint32_t)x, (uint32_t)x + 1u, (uint32_t)y, lo);
+    color_epilogue_h2(a.color, (uint32_t)x + 2u, (uint32_t)x + 3u, (uint32_t)y, hi);
+    const half4_t o[4] = {half4_t{lo.r.x, lo.g.x, lo.b.x, q[0].w}, half4_t{lo.r.y, lo.g.y, lo.b.y, q[1].w},
+                          half4_t{hi.r.x, hi.g.x, hi.b.x, q[2].w}, half4_t{hi.r.y, hi.g.y, hi.b.y, q[3].w}};
+    QuadH<FOUT>::store(dst + (long long)y * a.out.pitch, n, o);
+  }
+}
+
+static bool color_h_two_pixel(int fin, int fout) { return fin == FSR1_FORMAT_RGBA16F && fout == FSR1_FORMAT_RGBA16F; }
+
+void color_h_geometry(int fin, int fout, int width, int height, int* tiles_x, int* tiles_y) {
+  const int cols = color_h_two_pixel(fin, fout) ? kColorCols : kColorH4Cols;
+  *tiles_x = (width + cols - 1) / cols;
+  *tiles_y = (height + kColorRows - 1) / kColorRows;
+}
+
+hipError_t color_h_launch(const ColorPassArgs& a, int fin, int fout, hipStream_t stream) {
   const dim3 grid((unsigned)(a.tiles_x * a.tiles_y * a.frames)), block(kThreads);
-  hipLaunchKernelGGL(color_h_kernel, grid, block, 0, stream, a);
+  constexpr int F16 = FSR1_FORMAT_RGBA16F, U8 = FSR1_FORMAT_RGBA8_UNORM, U10 = FSR1_FORMAT_R10G10B10A2_UNORM;
+#define FSR1_COLOR_H4(I, O) hipLaunchKernelGGL((color_h4_kernel<I, O>), grid, block, 0, stream, a)
+  if (color_h_two_pixel(fin, fout)) hipLaunchKernelGGL(color_h_kernel, grid, block, 0, stream, a);
+  else if (fin == F16 && fout == U8) FSR1_COLOR_H4(F16, U8);
+  else if (fin == F16 && fout == U10) FSR1_COLOR_H4(F16, U10);
+  else if (fin == U8 && fout == F16) FSR1_COLOR_H4(U8, F16);
+  else if (fin == U8 && fout == U8) FSR1_COLOR_H4(U8, U8);
+  else if (fin == U8 && fout == U10) FSR1_COLOR_H4(U8, U10);
+  else if (fin == U10 && fout == F16) FSR1_COLOR_H4(U10, F16);
+  else if (fin == U10 && fout == U8) FSR1_COLOR_H4(U10, U8);
+  else if (fin == U10 && fout == U10) FSR1_COLOR_H4(U10, U10);
+  else return hipErrorInvalidValue;
+#undef FSR1_COLOR_H4
   return hipGetLastError();
 }
 

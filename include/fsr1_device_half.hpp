@@ -212,8 +212,11 @@ struct EasuHLds {
 // Phases 1 and 2 of the H kernel for the footprint [fx0, fx0+fw) x [fy0, fy0+fh).  FW, FH: compile-time extent (exact 2x).
 // THREADS: threads of the workgroup, all of which must make the call (it contains two barriers).  FMT: the image's storage format
 // (TexelH): only phase 1 sees it — the LDS records, and with them phase 2 and easu_h_pixel, are the same for every format.
-template <int FW, int FH, int THREADS = 256, int FMT = FSR1_FORMAT_RGBA16F>
-__device__ __forceinline__ void easu_h_stage(const EasuHLds& l, const ImageView& in, const char* in_frame, int fx0, int fy0, int fw_rt, int fh_rt, int tid) {
+// pre(c): applied once to every staged texel right after its load (the class-H colour prologue, fsr1_device_color_half.hpp): LDS then
+// holds the values the filter is to see, and the replicas of a clamped edge texel get the same value by construction.
+template <int FW, int FH, int THREADS, int FMT, class Pre>
+__device__ __forceinline__ void easu_h_stage(const EasuHLds& l, const ImageView& in, const char* in_frame, int fx0, int fy0, int fw_rt, int fh_rt, int tid,
+                                             const Pre& pre) {
   const int fw = FW ? FW : fw_rt, fh = FH ? FH : fh_rt;
   const int n = fw * fh - 1;  // the bottom-right corner texel is touched by no 12-tap window (no (2, 2) tap)
   const float inv_fw = 1.0f / (float)fw;
@@ -226,7 +229,7 @@ __device__ __forceinline__ void easu_h_stage(const EasuHLds& l, const ImageView&
     typedef TexelH<FMT> tex;
     constexpr uint32_t kPx = (uint32_t)sizeof(typename tex::T);
     auto stage = [&](int i, uint32_t off) {
-      const half4_t c = tex::load(*reinterpret_cast<const typename tex::T*>(base + (size_t)off));
+      const half4_t c = pre(tex::load(*reinterpret_cast<const typename tex::T*>(base + (size_t)off)));
       l.tex1[i] = half4_t{c.x, c.y, c.z, (half_t)(c.z * hlf + (c.x * hlf + c.y))};  // :535-538
     };
     if (fx0 >= 0 && fy0 >= 0 && fx0 + fw <= in.width && fy0 + fh <= in.height) {  // wave-uniform: nothing to clamp
@@ -268,6 +271,11 @@ __device__ __forceinline__ void easu_h_stage(const EasuHLds& l, const ImageView&
     }
   }
   __syncthreads();
+}
+
+template <int FW, int FH, int THREADS = 256, int FMT = FSR1_FORMAT_RGBA16F>
+__device__ __forceinline__ void easu_h_stage(const EasuHLds& l, const ImageView& in, const char* in_frame, int fx0, int fy0, int fw_rt, int fh_rt, int tid) {
+  easu_h_stage<FW, FH, THREADS, FMT>(l, in, in_frame, fx0, fy0, fw_rt, fh_rt, tid, [](half4_t c) { return c; });
 }
 
 // FsrEasuH for the pixel whose 'f' texel sits at footprint index f, sub-texel position ppp (= AH2(pp), :516).
@@ -399,3 +407,5 @@ __device__ __forceinline__ rgbh1_t rcas_pixel_h1(half_t bR, half_t bG, half_t bB
 }
 
 }  // namespace fsr1
+
+#include "fsr1_device_color_half.hpp"  // the class-H colour stages on a pixel pair (rgbh2_t)

@@ -111,7 +111,10 @@ enum {
    * division — bit-identical (fp32) to the CPU-evaluated FsrEasuF / FsrRcasF.
    * PACKED_FP16: the FsrEasuH / FsrRcasH entry points — packed binary16 arithmetic
    * (v_pk_*_f16), parity class "H" (vs the reference's CPU-evaluated H path).  Images: RGBA16F, RGBA8_UNORM or
-   * R10G10B10A2_UNORM (not RGBA32F); no colour stages, no row bands. */
+   * R10G10B10A2_UNORM (not RGBA32F); no row bands.  Colour stages fused into the EASU / RCAS dispatches need
+   * FSR1_FLAG_COLOR_STAGES_H beside it (below); without that bit packed fp16 with stages is FSR1_ERR_UNSUPPORTED, as it
+   * always was: the arithmetic of the stages is never chosen silently.  fsr1_color_dispatch runs the H stages under
+   * PACKED_FP16 alone. */
   FSR1_FLAG_MATH_EXACT = 1u << 4,
   FSR1_FLAG_MATH_PACKED_FP16 = 1u << 5,
   /* STRICT ("F-strict", round 6): EASU's stored image is BIT-IDENTICAL to FSR1_FLAG_MATH_EXACT's — i.e. to the CPU-evaluated
@@ -129,6 +132,12 @@ enum {
    * window mixes magnitudes (HDR noise) fails the test almost everywhere and runs at about the EXACT kernels' speed.  Exclusive with
    * MATH_EXACT and MATH_PACKED_FP16. */
   FSR1_FLAG_MATH_STRICT = 1u << 6,
+  /* With MATH_PACKED_FP16 (invalid without it): the colour stages handed to fsr1_easu_dispatch_ex, fsr1_rcas_dispatch_ex,
+   * fsr1_upscale_ex (params.flags) and fsr1_pipeline_upscale run in class H too — FsrSrtmH / FsrLfgaH / FsrSrtmInvH /
+   * FsrTepdC8H | C10H on pixel pairs in packed registers, bit-identical to the CPU-evaluated H path — fused into EASU-H's and
+   * RCAS-H's loads and stores.  The two fused H launches have no stages: fsr1_easu_rcas_fused_dispatch_ex and fused = 1
+   * stay FSR1_ERR_UNSUPPORTED, fused = 2 plans the two dispatches.  Accepted and without effect in fsr1_color_dispatch. */
+  FSR1_FLAG_COLOR_STAGES_H = 1u << 7,
   /* Diagnostics: never pick a shape-specialised kernel (e.g. the exact-2x variants, whose lanes own 2x2 output quads).
    * The specialised kernels run the same per-pixel arithmetic on the same values: results are bit-identical either way
    * (tests assert it); the flag exists so that this can be checked and the gain measured. */
@@ -197,6 +206,10 @@ int fsr1_easu_rcas_fused_dispatch(const fsr1_image* in, const fsr1_image* out, c
  * Arithmetic: binary32 in the reference's operation order, no contraction; with FSR1_FLAG_MATH_EXACT the two
  * reciprocals (ARcpF1) are IEEE divisions and every stage is bit-identical to the CPU-evaluated reference,
  * otherwise they are v_rcp_f32 (1 ulp).  FsrTepd*F's sqrt is correctly rounded in both modes.
+ * With FSR1_FLAG_MATH_PACKED_FP16 the stages are the reference's half-precision helpers (FsrSrtmH, FsrLfgaH, FsrSrtmInvH,
+ * FsrTepdC8H | C10H with FsrTepdDitH's binary32 dither narrowed once; ffx_fsr1.h:1017-1024, :1048-1056, :1124-1198): one
+ * native binary16 operation per reference operation on pixel pairs in packed registers, bit-identical to the
+ * CPU-evaluated H path; the same stage order, noise addressing and prologue / epilogue split.
  * ---------------------------------------------------------------------------------------------- */
 enum {
   FSR1_COLOR_SRTM = 1u << 0,
@@ -219,8 +232,10 @@ typedef struct fsr1_color_stages {
 /* Stand-alone pass: out[frame] = stages(in[frame]); in and out have the same size and may have different formats
  * (e.g. RGBA16F -> RGBA8_UNORM with FSR1_COLOR_TEPD_C8); in == out (in place) is allowed when the formats match.
  * flags: 0, FSR1_FLAG_MATH_EXACT, or FSR1_FLAG_MATH_PACKED_FP16 — the half-precision entry points FsrSrtmH /
- * FsrLfgaH / FsrSrtmInvH / FsrTepdC8H | C10H (+ their Hx2 forms; ffx_fsr1.h:1017-1024, :1048-1056, :1124-1198), RGBA16F
- * in and out, parity class "H" (bit-identical to the reference's CPU-evaluated H path). */
+ * FsrLfgaH / FsrSrtmInvH / FsrTepdC8H | C10H (+ their Hx2 forms; ffx_fsr1.h:1017-1024, :1048-1056, :1124-1198), parity
+ * class "H" (bit-identical to the reference's CPU-evaluated H path), for any pair of RGBA16F, RGBA8_UNORM and
+ * R10G10B10A2_UNORM (a UNORM texel is loaded as its decoded value rounded to binary16 and stored through the
+ * UNORM encode; in place when the formats match). */
 int fsr1_color_dispatch(const fsr1_image* in, const fsr1_image* out, const fsr1_color_stages* stages, uint32_t flags,
                         void* stream);
 
@@ -233,7 +248,10 @@ int fsr1_color_dispatch(const fsr1_image* in, const fsr1_image* out, const fsr1_
  * fsr1_rcas_dispatch_ex takes both; fsr1_easu_rcas_fused_dispatch_ex applies the prologue at the EASU loads and
  * the epilogue after RCAS.  `stages` == NULL (or no bits) is the plain pass.  out->format may differ from
  * in->format only as RGBA16F -> RGBA8_UNORM / R10G10B10A2_UNORM (the TEPD targets); the EASU->RCAS
- * intermediary of the fused kernel keeps in->format. */
+ * intermediary of the fused kernel keeps in->format.
+ * FSR1_FLAG_MATH_PACKED_FP16 | FSR1_FLAG_COLOR_STAGES_H: fsr1_easu_dispatch_ex and fsr1_rcas_dispatch_ex run the class-H stages for the same
+ * format pairs among RGBA16F, RGBA8_UNORM and R10G10B10A2_UNORM (RGBA16F -> UNORM is RCAS-H's own four-pixel kernel:
+ * the SDR chain's last pass); fsr1_easu_rcas_fused_dispatch_ex returns FSR1_ERR_UNSUPPORTED for packed fp16 with stages. */
 int fsr1_easu_dispatch_ex(const fsr1_image* in, const fsr1_image* out, const uint32_t con[16], uint32_t flags,
                           const fsr1_color_stages* stages, void* stream);
 int fsr1_rcas_dispatch_ex(const fsr1_image* in, const fsr1_image* out, const uint32_t con[4], uint32_t flags,
@@ -295,7 +313,10 @@ int fsr1_upscale(const fsr1_image* in, const fsr1_image* intermediary, const fsr
                  const fsr1_params* params, void* stream);
 
 /* fsr1_upscale with colour stages fused in (NULL = none): the prologue goes to EASU's loads, the epilogue to the
- * pass that writes `out` (RCAS, or EASU when use_rcas == 0), after the `hdr` square. */
+ * pass that writes `out` (RCAS, or EASU when use_rcas == 0), after the `hdr` square.
+ * FSR1_FLAG_MATH_PACKED_FP16 | FSR1_FLAG_COLOR_STAGES_H with stages: always the two dispatches (or EASU only) — fused = 2 plans them, fused = 1 and a
+ * NULL intermediary with use_rcas set are FSR1_ERR_UNSUPPORTED (the fused H launches have no stages).  The intermediary
+ * has in->format; out->format is in->format, or RGBA8_UNORM / R10G10B10A2_UNORM from an RGBA16F input. */
 int fsr1_upscale_ex(const fsr1_image* in, const fsr1_image* intermediary, const fsr1_image* out,
                     const fsr1_params* params, const fsr1_color_stages* stages, void* stream);
 
