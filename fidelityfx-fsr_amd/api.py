@@ -18,6 +18,8 @@ FORMAT_RGBA16F = 0
 FORMAT_RGBA32F = 1
 FORMAT_RGBA8_UNORM = 2
 FORMAT_R10G10B10A2_UNORM = 3
+FORMAT_RGB16F_PLANAR = 4  # three planes R, G, B: a (N,3,H,W) tensor, marked with Planar()
+FORMAT_RGB32F_PLANAR = 5
 
 FLAG_HDR_SQUARE = 1 << 0
 FLAG_RCAS_DENOISE = 1 << 1
@@ -83,12 +85,53 @@ def AU1_AH1_AF1(f):
 # --------------------------------------------------------------------------------------------------
 # images
 # --------------------------------------------------------------------------------------------------
+class Planar:
+    """Marks a CUDA tensor shaped (3,H,W) or (N,3,H,W), float16 or float32, as planar RGB (FORMAT_RGB16F_PLANAR / RGB32F_PLANAR): what
+    a decoder or a model hands over, taken as it is — no permute, no alpha.  Rows may be padded (a row stride larger than W); the
+    planes must follow each other row stride x H apart, which is how the C ABI finds them.  Pass it wherever an image tensor goes
+    (easu, rcas, FSR_Filter, Pipeline.upscale); a bare tensor is always read as interleaved, so a (3,H,4) tensor stays RGBA."""
+
+    def __init__(self, t):
+        self.t = t
+
+    def image(self):
+        import torch
+        t = self.t
+        if not t.is_cuda:
+            raise Fsr1Error("image tensors must live on the GPU (got %s); there is no CPU path" % t.device)
+        if t.dim() == 3:
+            t = t.unsqueeze(0)
+        if t.dim() != 4 or t.shape[1] != 3:
+            raise Fsr1Error("expected (N,3,H,W) planar RGB, got %s" % (tuple(self.t.shape),))
+        if t.dtype == torch.float16:
+            fmt, es = FORMAT_RGB16F_PLANAR, 2
+        elif t.dtype == torch.float32:
+            fmt, es = FORMAT_RGB32F_PLANAR, 4
+        else:
+            raise Fsr1Error("planar images are float16 or float32, got %s" % t.dtype)
+        n, _, h, w = t.shape
+        sn, sp, sh, sw = t.stride()
+        if sw != 1:
+            raise Fsr1Error("planes must be dense along x")
+        if sp != sh * h:
+            raise Fsr1Error("plane stride %d elements is not row stride %d x height %d: the planes of a frame must follow each other" % (sp, sh, h))
+        _check_strides(n, 3 * h, w, sn, sh, 1)
+        return fsr1_image(t.data_ptr(), w, h, fmt, n, sh * es, sn * es if n > 1 else 0)
+
+    def empty_like(self):
+        import torch
+        return Planar(torch.empty_like(self.t))
+
+
 def image_of(t):
     """fsr1_image descriptor of a CUDA torch tensor:
       float16 / float32 / uint8, shaped (H,W,4) or (N,H,W,4)  -> RGBA16F / RGBA32F / RGBA8_UNORM
       int32, shaped (H,W) or (N,H,W)                          -> R10G10B10A2_UNORM (one packed word per pixel)
+      Planar(float16 / float32, shaped (3,H,W) or (N,3,H,W))  -> RGB16F_PLANAR / RGB32F_PLANAR
     Row and frame strides are honoured; the innermost (x[, channel]) dims must be dense."""
     import torch
+    if isinstance(t, Planar):
+        return t.image()
     if not t.is_cuda:
         raise Fsr1Error("image tensors must live on the GPU (got %s); there is no CPU path" % t.device)
     if t.dtype == torch.int32:
@@ -338,7 +381,7 @@ class FSR_Filter:
         self._input, self._output, self._hdr = input, output, hdr
         # FSR_Filter.cpp:72-73 creates the EASU->RCAS intermediary at display size; here it has the
         # output's format (RGBA16F/RGBA32F) and batch size.
-        self.m_intermediary = None if self.fused is True else torch.empty_like(output)
+        self.m_intermediary = None if self.fused is True else (output.empty_like() if isinstance(output, Planar) else torch.empty_like(output))
 
     def OnDestroyWindowSizeDependentResources(self):
         self.m_intermediary = None

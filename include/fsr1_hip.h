@@ -52,7 +52,7 @@ void FsrRcasCon(uint32_t* con, float sharpness);
 uint32_t AU1_AH1_AF1(float f);
 
 /* ------------------------------------------------------------------------------------------------
- * Images.  Pixels are RGBA interleaved; rows are row_pitch_bytes apart, frames (independent
+ * Images.  Pixels are RGBA interleaved (or, formats 4 and 5, three RGB planes); rows are row_pitch_bytes apart, frames (independent
  * images of one batch, processed by one launch) frame_stride_bytes apart.
  * ---------------------------------------------------------------------------------------------- */
 typedef enum fsr1_format {
@@ -75,7 +75,22 @@ typedef enum fsr1_format {
    * alpha = 1.  The fused launch passes every EASU result through store and load before RCAS reads it, so it stays bit-identical
    * to the two dispatches with an intermediary of out's format.  in->format == out->format, as for F. */
   FSR1_FORMAT_RGBA8_UNORM = 2,        /* 4 B/pixel: R bits 0-7, G 8-15, B 16-23, A 24-31 */
-  FSR1_FORMAT_R10G10B10A2_UNORM = 3   /* 4 B/pixel: R bits 0-9, G 10-19, B 20-29, A 30-31 */
+  FSR1_FORMAT_R10G10B10A2_UNORM = 3,  /* 4 B/pixel: R bits 0-9, G 10-19, B 20-29, A 30-31 */
+  /* Planar RGB — what a PyTorch process holds: a contiguous (N,3,H,W) tensor, or one whose rows are padded.  No alpha.  A frame is
+   * three planes R, G, B of `height` rows of `width` scalars each, rows row_pitch_bytes apart (0 = width x element size); plane p of
+   * frame f starts at data + f * frame_stride_bytes + p * row_pitch_bytes * height; frame_stride_bytes 0 = 3 * pitch * height.
+   * Pointer, pitch and frame stride must be multiples of the ELEMENT size (2 or 4 bytes) and of nothing larger: where they are also
+   * multiples of 8 / 16 bytes the kernels move four columns of a plane row per access, otherwise element by element.
+   * Accepted by fsr1_easu_dispatch, fsr1_rcas_dispatch, fsr1_upscale[_ex] / fsr1_upscale_plan / fsr1_pipeline_upscale without colour
+   * stages (fused = 2 plans the two dispatches), in->format == out->format (and the intermediary's), with the F arithmetic: default or
+   * FSR1_FLAG_MATH_EXACT; FSR1_FLAG_MATH_STRICT takes the EXACT kernels for both passes, as it does for RGBA32F (there is no strict
+   * variant on planar storage).  HDR_SQUARE, RCAS_DENOISE, the OUTPUT_* store policies and FRAMES_OVERLAP work as for interleaved
+   * images; every value is the one the interleaved kernels store for the same pixels with alpha 1.  FSR1_ERR_UNSUPPORTED (the message
+   * says "planar"): FSR1_FLAG_MATH_PACKED_FP16, colour stages, row bands, the fused launches (fused = 1, or use_rcas without an
+   * intermediary), FSR1_FLAG_RCAS_PASSTHROUGH_ALPHA (there is no alpha), and a planar image on one side with an interleaved one on
+   * the other. */
+  FSR1_FORMAT_RGB16F_PLANAR = 4,      /* binary16 planes, 6 B/pixel */
+  FSR1_FORMAT_RGB32F_PLANAR = 5       /* binary32 planes, 12 B/pixel */
 } fsr1_format;
 
 typedef struct fsr1_image {

@@ -1,0 +1,125 @@
+#!/usr/bin/env python3
+"""Planar RGB (FORMAT_RGB16F_PLANAR) against RGBA16F at 1920x1080 -> 3840x2160, default arithmetic, one frame per call.
+
+  python tools/planar_bench.py --out profiles/planar_1080p_to_4k.json
+
+Every configuration is timed between two events on the current stream over `--calls` back-to-back calls, seven windows per
+configuration with the configurations alternating; "cold" configurations walk a ring of buffer sets larger than the 256 MB
+Infinity Cache, "resident" ones stay on one set.  Needs a GPU: there is no fallback."""
+import argparse
+import importlib
+import json
+import os
+import statistics
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def smi():
+    """sclk / mclk / power as rocm-smi reports them after the run (read-only query); the raw text when it is not JSON."""
+    try:
+        out = subprocess.run(["rocm-smi", "--showclocks", "--showpower", "--json"], capture_output=True, text=True, timeout=60).stdout
+        try:
+            card = sorted(json.loads(out).items())[0][1]
+            return {k: v for k, v in card.items() if any(s in k.lower() for s in ("sclk", "mclk", "power"))}
+        except Exception:
+            return out.strip()[:600]
+    except Exception as e:  # the tool is missing: say so in the file
+        return "rocm-smi unavailable: %s" % e
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", required=True)
+    ap.add_argument("--calls", type=int, default=300)
+    ap.add_argument("--windows", type=int, default=7)
+    ap.add_argument("--ring", type=int, default=8)
+    args = ap.parse_args()
+    import torch
+    fsr = importlib.import_module("fidelityfx-fsr_amd")
+    fsr.load()
+    if not torch.cuda.is_available():
+        raise SystemExit("planar_bench needs a GPU")
+    iw, ih, ow, oh = 1920, 1080, 3840, 2160
+    con, rcon = fsr.FsrEasuCon(iw, ih, iw, ih, ow, oh), fsr.FsrRcasCon(0.25)
+    P = fsr.Planar
+    rgba = torch.from_numpy(fsr.frames.synthetic_frame(iw, ih, k=0)).cuda()
+    chw = rgba[..., :3].permute(2, 0, 1).contiguous()
+
+    def ring(make):
+        return [make() for _ in range(args.ring)]
+
+    z = lambda *s: torch.zeros(*s, dtype=torch.float16, device="cuda")  # noqa: E731
+    p_in, p_mid, p_out = ring(lambda: chw.clone()), ring(lambda: z(3, oh, ow)), ring(lambda: z(3, oh, ow))
+    i_in, i_mid, i_out = ring(lambda: rgba.clone()), ring(lambda: z(oh, ow, 4)), ring(lambda: z(oh, ow, 4))
+    for k in range(args.ring):  # real intermediaries for the RCAS-only configurations
+        fsr.easu(P(p_in[k]), P(p_mid[k]), con=con)
+        fsr.easu(i_in[k], i_mid[k], con=con)
+    ones = torch.ones(1, ih, iw, 1, dtype=torch.float16, device="cuda")
+
+    def wrapped(k):
+        """What a caller of the interleaved ABI does for a (1,3,H,W) tensor today."""
+        x = torch.cat([p_in[k].unsqueeze(0).permute(0, 2, 3, 1), ones], -1)
+        fsr.easu(x, i_mid[k].unsqueeze(0), con=con)
+        fsr.rcas(i_mid[k].unsqueeze(0), i_out[k].unsqueeze(0), con=rcon)
+        return i_out[k].unsqueeze(0)[..., :3].permute(0, 3, 1, 2).contiguous()
+
+    def chain_planar(k):
+        fsr.easu(P(p_in[k]), P(p_mid[k]), con=con)
+        fsr.rcas(P(p_mid[k]), P(p_out[k]), con=rcon)
+
+    def chain_rgba(k):
+        fsr.easu(i_in[k], i_mid[k], con=con)
+        fsr.rcas(i_mid[k], i_out[k], con=rcon)
+
+    configs = {
+        "rcas_planar_cold": (lambda k: fsr.rcas(P(p_mid[k]), P(p_out[k]), con=rcon), args.ring),
+        "rcas_rgba16f_cold": (lambda k: fsr.rcas(i_mid[k], i_out[k], con=rcon), args.ring),
+        "rcas_planar_resident": (lambda k: fsr.rcas(P(p_mid[k]), P(p_out[k]), con=rcon), 1),
+        "rcas_rgba16f_resident": (lambda k: fsr.rcas(i_mid[k], i_out[k], con=rcon), 1),
+        "easu_planar": (lambda k: fsr.easu(P(p_in[k]), P(p_mid[k]), con=con), args.ring),
+        "easu_rgba16f": (lambda k: fsr.easu(i_in[k], i_mid[k], con=con), args.ring),
+        "chain_planar": (chain_planar, args.ring),
+        "chain_rgba16f": (chain_rgba, args.ring),
+        "chain_rgba16f_permute_wrapped": (wrapped, args.ring),
+    }
+    # the planar chain and the wrapped interleaved chain compute the same image
+    chain_planar(0)
+    same = bool(torch.equal(p_out[0].unsqueeze(0), wrapped(0)))
+    for fn, n in configs.values():  # warm every kernel on every buffer set
+        for k in range(n):
+            fn(k)
+    torch.cuda.synchronize()
+    times = {name: [] for name in configs}
+    for _ in range(args.windows):
+        for name, (fn, n) in configs.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for c in range(args.calls):
+                fn(c % n)
+            e1.record()
+            e1.synchronize()
+            times[name].append(e0.elapsed_time(e1) * 1000.0 / args.calls)
+    doc = {
+        "what": "planar RGB fp16 against RGBA16F, %dx%d -> %dx%d, default arithmetic, one frame per call; %d calls per window between two events on one "
+                "stream, %d windows per configuration, the configurations alternating; cold = a ring of %d buffer sets, resident = one set"
+                % (iw, ih, ow, oh, args.calls, args.windows, args.ring),
+        "device": torch.cuda.get_device_name(0),
+        "clocks_and_power_after_the_run": smi(),
+        "planar_chain_equals_permute_wrapped_chain": same,
+        "us_per_call": {k: {"median": round(statistics.median(v), 2), "min": round(min(v), 2), "max": round(max(v), 2)} for k, v in times.items()},
+        "build_id": fsr._lib.build_id(),
+    }
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(doc, f, indent=1)
+        f.write("\n")
+    print(json.dumps(doc["us_per_call"], indent=1))
+    print("planar == wrapped:", same)
+
+
+if __name__ == "__main__":
+    main()
