@@ -20,6 +20,7 @@ FORMAT_RGBA8_UNORM = 2
 FORMAT_R10G10B10A2_UNORM = 3
 FORMAT_RGB16F_PLANAR = 4  # three planes R, G, B: a (N,3,H,W) tensor, marked with Planar()
 FORMAT_RGB32F_PLANAR = 5
+FORMAT_RGB8_UNORM_PLANAR = 6  # uint8 planes: what a decoder hands over
 
 FLAG_HDR_SQUARE = 1 << 0
 FLAG_RCAS_DENOISE = 1 << 1
@@ -86,7 +87,8 @@ def AU1_AH1_AF1(f):
 # images
 # --------------------------------------------------------------------------------------------------
 class Planar:
-    """Marks a CUDA tensor shaped (3,H,W) or (N,3,H,W), float16 or float32, as planar RGB (FORMAT_RGB16F_PLANAR / RGB32F_PLANAR): what
+    """Marks a CUDA tensor shaped (3,H,W) or (N,3,H,W), float16, float32 or uint8, as planar RGB (FORMAT_RGB16F_PLANAR / RGB32F_PLANAR /
+    RGB8_UNORM_PLANAR): what
     a decoder or a model hands over, taken as it is — no permute, no alpha.  Rows may be padded (a row stride larger than W); the
     planes must follow each other row stride x H apart, which is how the C ABI finds them.  Pass it wherever an image tensor goes
     (easu, rcas, FSR_Filter, Pipeline.upscale); a bare tensor is always read as interleaved, so a (3,H,4) tensor stays RGBA."""
@@ -107,8 +109,10 @@ class Planar:
             fmt, es = FORMAT_RGB16F_PLANAR, 2
         elif t.dtype == torch.float32:
             fmt, es = FORMAT_RGB32F_PLANAR, 4
+        elif t.dtype == torch.uint8:
+            fmt, es = FORMAT_RGB8_UNORM_PLANAR, 1
         else:
-            raise Fsr1Error("planar images are float16 or float32, got %s" % t.dtype)
+            raise Fsr1Error("planar images are float16, float32 or uint8, got %s" % t.dtype)
         n, _, h, w = t.shape
         sn, sp, sh, sw = t.stride()
         if sw != 1:
@@ -127,7 +131,7 @@ def image_of(t):
     """fsr1_image descriptor of a CUDA torch tensor:
       float16 / float32 / uint8, shaped (H,W,4) or (N,H,W,4)  -> RGBA16F / RGBA32F / RGBA8_UNORM
       int32, shaped (H,W) or (N,H,W)                          -> R10G10B10A2_UNORM (one packed word per pixel)
-      Planar(float16 / float32, shaped (3,H,W) or (N,3,H,W))  -> RGB16F_PLANAR / RGB32F_PLANAR
+      Planar(float16 / float32 / uint8, shaped (3,H,W) or (N,3,H,W))  -> RGB16F_PLANAR / RGB32F_PLANAR / RGB8_UNORM_PLANAR
     Row and frame strides are honoured; the innermost (x[, channel]) dims must be dense."""
     import torch
     if isinstance(t, Planar):

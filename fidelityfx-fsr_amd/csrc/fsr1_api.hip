@@ -131,13 +131,13 @@ static bool packed_format_ok(int fmt) {
 
 // Planar RGB (three planes per frame, fsr1_hip.h): served by the plain EASU and RCAS dispatches in F arithmetic; everything else
 // refuses it with a message that says "planar".
-static bool is_planar(int fmt) { return fmt == FSR1_FORMAT_RGB16F_PLANAR || fmt == FSR1_FORMAT_RGB32F_PLANAR; }
+static bool is_planar(int fmt) { return fmt == FSR1_FORMAT_RGB16F_PLANAR || fmt == FSR1_FORMAT_RGB32F_PLANAR || fmt == FSR1_FORMAT_RGB8_UNORM_PLANAR; }
 static int image_planes(int fmt) { return is_planar(fmt) ? 3 : 1; }
 static bool any_planar(const fsr1_image* a, const fsr1_image* b) { return (a && is_planar(a->format)) || (b && is_planar(b->format)); }
 
 // bytes of the unit rows are made of: an interleaved pixel, or one element of a plane
 static size_t pixel_bytes(int fmt) {
-  if (is_planar(fmt)) return fmt == FSR1_FORMAT_RGB32F_PLANAR ? 4 : 2;
+  if (is_planar(fmt)) return fmt == FSR1_FORMAT_RGB32F_PLANAR ? 4 : (fmt == FSR1_FORMAT_RGB16F_PLANAR ? 2 : 1);
   return fmt == FSR1_FORMAT_RGBA32F ? 16 : (fmt == FSR1_FORMAT_RGBA16F ? 8 : 4);
 }
 
@@ -148,7 +148,7 @@ static int check_image(const fsr1_image* im, const char* name, ImageView* v) {
     return fail(FSR1_ERR_INVALID_ARGUMENT, "%s: bad extent %dx%dx%d", name, im->width, im->height, im->frames);
   if (im->width > (1 << 20) || im->height > (1 << 20))  // pixel coordinates stay exact in binary32 with room to spare
     return fail(FSR1_ERR_UNSUPPORTED, "%s: extent %dx%d beyond 2^20 pixels per side", name, im->width, im->height);
-  if (im->format < FSR1_FORMAT_RGBA16F || im->format > FSR1_FORMAT_RGB32F_PLANAR)
+  if (im->format < FSR1_FORMAT_RGBA16F || im->format > FSR1_FORMAT_RGB8_UNORM_PLANAR)
     return fail(FSR1_ERR_UNSUPPORTED, "%s: unsupported format %d", name, im->format);
   const size_t px = pixel_bytes(im->format);
   const long long pitch = im->row_pitch_bytes ? im->row_pitch_bytes : (long long)im->width * (long long)px;
@@ -437,7 +437,8 @@ static int easu_planar_dispatch(const fsr1_image* in, const fsr1_image* out, Eas
     a.fp_h = kTileH / 2 + 3;
   }
   if (int rc = check_grid("easu", a.tiles_x, a.tiles_y, a.frames)) return rc;
-  const bool wide = planar_aligned(out, a.out, 2 * pixel_bytes(out->format));  // the exact-2x variant's pair stores
+  // the exact-2x variant's pair stores; 8-bit planes: its dword stores
+  const bool wide = planar_aligned(out, a.out, out->format == FSR1_FORMAT_RGB8_UNORM_PLANAR ? 4 : 2 * pixel_bytes(out->format));
   const hipError_t e = easu_planar_launch(a, in->format, exact, s2, wide, static_cast<hipStream_t>(stream));
   if (e != hipSuccess) return hip_fail(e, "easu launch");
   return FSR1_OK;
@@ -794,7 +795,7 @@ static int upscale_decide(const char* who, const fsr1_image* in, bool have_inter
   for (const fsr1_image* im : {in, out}) {
     if (im->width <= 0 || im->height <= 0 || im->frames <= 0)
       return fail(FSR1_ERR_INVALID_ARGUMENT, "%s: bad %s extent %dx%dx%d", who, im == in ? "input" : "output", im->width, im->height, im->frames);
-    if (im->format < FSR1_FORMAT_RGBA16F || im->format > FSR1_FORMAT_RGB32F_PLANAR)
+    if (im->format < FSR1_FORMAT_RGBA16F || im->format > FSR1_FORMAT_RGB8_UNORM_PLANAR)
       return fail(FSR1_ERR_UNSUPPORTED, "%s: unsupported %s format %d", who, im == in ? "input" : "output", im->format);
   }
   const bool planar = any_planar(in, out);

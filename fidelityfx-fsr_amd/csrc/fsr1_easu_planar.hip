@@ -1,16 +1,17 @@
-// EASU on planar RGB images (FSR1_FORMAT_RGB16F_PLANAR / RGB32F_PLANAR): a (N,3,H,W) tensor in, one out, no permute and no
+// EASU on planar RGB images (FSR1_FORMAT_RGB16F_PLANAR / RGB32F_PLANAR / RGB8_UNORM_PLANAR): a (N,3,H,W) tensor in, one out, no permute and no
 // alpha plane either side.
 //
 // The filter is fsr1_easu.hip's: the same 64 x 16 tiles of four waves, the same LDS records (R, G, B, luma*2 | analysis), the same
 // per-pixel functions (easu_quad_row / easu_quad_pixel / easu_pixel_with_bounds, easu_clamp) on the same values — every pixel is the
 // value the interleaved kernel stores.  The two ends that touch memory are this file's (include/fsr1_device_planar.hpp):
-//   staging  one wave per footprint row, the three plane-row bases scalar, three coalesced 2- or 4-byte loads per texel, all of a
-//            wave's loads issued before the first conversion;
+//   staging  one wave per footprint row, the three plane-row bases scalar, three coalesced 1-, 2- or 4-byte loads per texel, all of a
+//            wave's loads issued before the first conversion (8-bit codes: the decode of Pixel<RGBA8_UNORM>);
 //   stores   exact 2x: a lane's 2 x 2 quad starts at an odd column (the tiles are shifted by one pixel), so its row pair is not aligned
 //            in a plane.  Each lane takes the left pixel of the lane to its right through one DPP move per channel and stores the
 //            even-aligned pair {own right, neighbour's left} per plane and row; the tile's first / last quad column store one scalar.
 //            Quads on the image border are filtered like all others (their window lies in the clamped footprint) and only their
-//            stores are predicated, so that every lane is there for its neighbour.  WIDE = false — base, pitch or a stride not a
+//            stores are predicated, so that every lane is there for its neighbour.  8-bit planes: a pair is two bytes, so the even
+//            quad columns collect their neighbour's pair too and store one dword (planar_store_quad_row_u8).  WIDE = false — base, pitch or a stride not a
 //            multiple of the pair, e.g. a tightly packed odd width — stores element by element;
 //            other ratios: a lane owns a column (easu_lane_column), one scalar store per plane and pixel.
 #include "fsr1_device.h"
@@ -54,23 +55,27 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(7
     const int f_idx = (qy + 1) * kS2W + (qx + 1);
     char* const o0 = out_frame + (long long)oya * a.out.pitch + (long long)oxa * (long long)sizeof(elem_t);
     const float4_t A[4] = {l.ana[f_idx], l.ana[f_idx + 1], l.ana[f_idx + kS2W], l.ana[f_idx + kS2W + 1]};
+    auto store_row = [&](char* o, rgbf_t left, rgbf_t right, bool row_in) {
+      if constexpr (FMT == FSR1_FORMAT_RGB8_UNORM_PLANAR) planar_store_quad_row_u8<WIDE>(o, ops, left, right, qx, oxa, W, row_in, stream);
+      else planar_store_quad_row<FMT, WIDE>(o, ops, left, right, qx, row_in, xin0, xin1, xin2, stream);
+    };
     EasuBounds m;
     if constexpr (!EXACT) {
       // the default arithmetic's row pairs (easu_quad_row): bounds of the first row's tap values
       rgbf_t q0, q1;
       easu_quad_row<true>(l, f_idx, 0.25f, A, m, q0, q1);
-      planar_store_quad_row<FMT, WIDE>(o0, ops, easu_clamp<EXACT>(m, q0, hdr), easu_clamp<EXACT>(m, q1, hdr), qx, yin0, xin0, xin1, xin2, stream);
+      store_row(o0, easu_clamp<EXACT>(m, q0, hdr), easu_clamp<EXACT>(m, q1, hdr), yin0);
       easu_quad_row<false>(l, f_idx, 0.75f, A, m, q0, q1);
-      planar_store_quad_row<FMT, WIDE>(o0 + a.out.pitch, ops, easu_clamp<EXACT>(m, q0, hdr), easu_clamp<EXACT>(m, q1, hdr), qx, yin1, xin0, xin1, xin2, stream);
+      store_row(o0 + a.out.pitch, easu_clamp<EXACT>(m, q0, hdr), easu_clamp<EXACT>(m, q1, hdr), yin1);
     } else {
       // EXACT: pixel by pixel with the quad's analyses shared and the bounds of the first pixel's taps
       const rgbf_t q00 = easu_quad_pixel<EXACT, true>(l, f_idx, 0.25f, 0.25f, A, m);
       const rgbf_t p00 = easu_clamp<EXACT>(m, q00, hdr);
       const rgbf_t p10 = easu_clamp<EXACT>(m, easu_quad_pixel<EXACT, false>(l, f_idx, 0.75f, 0.25f, A, m), hdr);
-      planar_store_quad_row<FMT, WIDE>(o0, ops, p00, p10, qx, yin0, xin0, xin1, xin2, stream);
+      store_row(o0, p00, p10, yin0);
       const rgbf_t p01 = easu_clamp<EXACT>(m, easu_quad_pixel<EXACT, false>(l, f_idx, 0.25f, 0.75f, A, m), hdr);
       const rgbf_t p11 = easu_clamp<EXACT>(m, easu_quad_pixel<EXACT, false>(l, f_idx, 0.75f, 0.75f, A, m), hdr);
-      planar_store_quad_row<FMT, WIDE>(o0 + a.out.pitch, ops, p01, p11, qx, yin1, xin0, xin1, xin2, stream);
+      store_row(o0 + a.out.pitch, p01, p11, yin1);
     }
     return;
   }
@@ -119,7 +124,7 @@ static hipError_t easu_planar_launch_one(const EasuArgs& a, hipStream_t stream) 
 }
 
 // s2: the exact-2x variant (the host has checked con0 and laid the grid out for the shifted tiles); wide: its pair stores (the host
-// has checked the output's base, pitch, plane and frame stride against two elements).  The generic variant has no wide form.
+// has checked the output's base, pitch, plane and frame stride against two elements; 8-bit planes: its dword stores, against four).  The generic variant has no wide form.
 hipError_t easu_planar_launch(const EasuArgs& a, int fmt, bool exact, bool s2, bool wide, hipStream_t stream) {
   const bool hdr = (a.flags & FSR1_FLAG_HDR_SQUARE) != 0;
 #define FSR1_PLANAR_H(F, E, S, V) return hdr ? easu_planar_launch_one<F, E, S, true, V>(a, stream) : easu_planar_launch_one<F, E, S, false, V>(a, stream)
@@ -139,6 +144,7 @@ hipError_t easu_planar_launch(const EasuArgs& a, int fmt, bool exact, bool s2, b
   switch (fmt) {
     case FSR1_FORMAT_RGB16F_PLANAR: FSR1_PLANAR_E(FSR1_FORMAT_RGB16F_PLANAR);
     case FSR1_FORMAT_RGB32F_PLANAR: FSR1_PLANAR_E(FSR1_FORMAT_RGB32F_PLANAR);
+    case FSR1_FORMAT_RGB8_UNORM_PLANAR: FSR1_PLANAR_E(FSR1_FORMAT_RGB8_UNORM_PLANAR);
     default: return hipErrorInvalidValue;
   }
 #undef FSR1_PLANAR_E

@@ -1,15 +1,17 @@
-// RCAS on planar RGB images (FSR1_FORMAT_RGB16F_PLANAR / RGB32F_PLANAR): a strip kernel of its own, no LDS, no barrier.
+// RCAS on planar RGB images (FSR1_FORMAT_RGB16F_PLANAR / RGB32F_PLANAR / RGB8_UNORM_PLANAR): a strip kernel of its own, no LDS, no barrier.
 //
 // RCAS is the pass that is bound by its bytes, and an interleaved RGBA16F pixel carries a quarter of them as
 // an alpha that is read and written as 1: three planes move 12 B per pixel where RGBA16F moves 16.
 //   * a wave owns a 256-column strip and walks it row by row — downwards in even strip rows, upwards in odd ones, so that vertically
 //     adjacent strips meet at the rows they share (fsr1_rcas_kernel.h, UP); a lane owns FOUR adjacent columns: per row and plane one
-//     8-byte (fp16) or 16-byte (fp32) load and one store of the same width;
+//     8-byte (fp16) or 16-byte (fp32) load and one store of the same width; 8-bit planes: one DWORD each way, the raw rows stay in
+//     flight as packed dwords (three registers a row), a row is decoded once, as it becomes `next`, and the four results of a plane
+//     are encoded and merged before the store: 3 B in and 3 B out per pixel where RGBA8 moves 4 + 4;
 //   * of the horizontal taps of a lane's four pixels, six are its own registers and two are the facing pixels of the adjacent lanes,
 //     fetched in fp32 by DPP wave shifts: six moves per four pixels (the interleaved kernel: six per two);
 //   * lanes 0 and 63 load the apron column, one element per plane, which the DPP move leaves in place for exactly those lanes;
 //   * rows live in a register ring: prev / cur / next as fp32, raw rows in flight ahead of the arithmetic (2 deep for a launch short
-//     of waves, 4 for batches);
+//     of waves, 4 for batches; 8-bit planes: always 4);
 //   * the per-pixel function is rcas_pixel<EXACT> with the interleaved kernel's operand order (b above, h below whichever way the
 //     strip walks): every value is the one that kernel stores for the same pixels with alpha 1;
 //   * taps outside the image are 0; strips wholly inside the image run a branch-free body, the image's first / last wave-column the
@@ -55,7 +57,8 @@ __device__ __forceinline__ void rcas_planar_strip(const RcasArgs& a, int frame, 
   static_assert(!UP || INTERIOR, "only strips that store every row walk up");
   auto row_y = [&](int k) { return UP ? y0 + rows - 1 - k : y0 + k; };  // k-th row of the walk, k = -1 .. rows
   struct row_t { quad_t p[3]; elem_t halo[3]; };
-  const quad_t zero4 = {(elem_t)0, (elem_t)0, (elem_t)0, (elem_t)0};
+  typedef Plane<FMT> P;
+  const quad_t zero4 = P::make4((elem_t)0, (elem_t)0, (elem_t)0, (elem_t)0);
   auto load = [&](int y, row_t& r) {
     const bool row_in = INTERIOR || (y >= 0 && y < H);  // wave-uniform
 #pragma unroll
@@ -66,7 +69,7 @@ __device__ __forceinline__ void rcas_planar_strip(const RcasArgs& a, int frame, 
           r.p[c] = *reinterpret_cast<const quad_t*>(src + zext(off));
         } else {
           const elem_t* const e = reinterpret_cast<const elem_t*>(src + zext(off));
-          r.p[c] = quad_t{e[0], e[1], e[2], e[3]};
+          r.p[c] = P::make4(e[0], e[1], e[2], e[3]);
         }
         r.halo[c] = *reinterpret_cast<const elem_t*>(src + zext(hoff));
         if constexpr (XEDGE) {
@@ -80,10 +83,10 @@ __device__ __forceinline__ void rcas_planar_strip(const RcasArgs& a, int frame, 
           if (WIDE && ok[3]) {
             r.p[c] = *reinterpret_cast<const quad_t*>(e);
           } else {
-            if (ok[0]) r.p[c].x = e[0];
-            if (ok[1]) r.p[c].y = e[1];
-            if (ok[2]) r.p[c].z = e[2];
-            if (ok[3]) r.p[c].w = e[3];
+            if (ok[0]) P::template put<0>(r.p[c], e[0]);
+            if (ok[1]) P::template put<1>(r.p[c], e[1]);
+            if (ok[2]) P::template put<2>(r.p[c], e[2]);
+            if (ok[3]) P::template put<3>(r.p[c], e[3]);
           }
           if (halo_ok) r.halo[c] = *reinterpret_cast<const elem_t*>(src + zext(hoff));
         }
@@ -92,8 +95,9 @@ __device__ __forceinline__ void rcas_planar_strip(const RcasArgs& a, int frame, 
   };
   struct px4_t { rgb_t v[4]; };
   auto rgb4 = [](const row_t& r) {
-    return px4_t{{rgb_t{(float)r.p[0].x, (float)r.p[1].x, (float)r.p[2].x}, rgb_t{(float)r.p[0].y, (float)r.p[1].y, (float)r.p[2].y},
-                  rgb_t{(float)r.p[0].z, (float)r.p[1].z, (float)r.p[2].z}, rgb_t{(float)r.p[0].w, (float)r.p[1].w, (float)r.p[2].w}}};
+#define FSR1_RCASP_COL(I) rgb_t{P::load(P::template get<I>(r.p[0])), P::load(P::template get<I>(r.p[1])), P::load(P::template get<I>(r.p[2]))}
+    return px4_t{{FSR1_RCASP_COL(0), FSR1_RCASP_COL(1), FSR1_RCASP_COL(2), FSR1_RCASP_COL(3)}};
+#undef FSR1_RCASP_COL
   };
   // ring of raw rows in registers, loads kAhead rows ahead of the arithmetic; the row loop is unrolled by the ring (static indices)
   constexpr int kRing = RING, kAhead = kRing - 1;  // divides every strip height the launcher picks (multiples of 8)
@@ -117,7 +121,7 @@ __device__ __forceinline__ void rcas_planar_strip(const RcasArgs& a, int frame, 
       load(row_y(min(r0 + k + kAhead, rows)), q[(k + kAhead) % kRing]);  // past the end: re-reads the last row (harmless, branch-free)
       const row_t& c = q[k];
       const px4_t next = rgb4(q[(k + 1) % kRing]);
-      const rgb_t hal = {(float)c.halo[0], (float)c.halo[1], (float)c.halo[2]};
+      const rgb_t hal = {P::load(c.halo[0]), P::load(c.halo[1]), P::load(c.halo[2])};
       // pixel 0's left tap = the left lane's pixel 3, pixel 3's right tap = the right lane's pixel 0; lanes 0 / 63 keep their apron texel
       const rgb_t d0 = planar_neighbour<kDppWaveShr1>(hal, cur.v[3]), f3 = planar_neighbour<kDppWaveShl1>(hal, cur.v[0]);
       const px4_t& above = UP ? next : prev;  // b is the tap above, h the one below (ffx_fsr1.h:697-707), whichever way the strip walks
@@ -131,14 +135,13 @@ __device__ __forceinline__ void rcas_planar_strip(const RcasArgs& a, int frame, 
 #pragma unroll
         for (int p = 0; p < 3; ++p) {
           char* const dst = out_frame + p * ops + (long long)y * a.out.pitch + zext(off);
-          const elem_t e0 = Plane<FMT>::store(out[p][0]), e1 = Plane<FMT>::store(out[p][1]), e2 = Plane<FMT>::store(out[p][2]), e3 = Plane<FMT>::store(out[p][3]);
           if (WIDE && ok[3]) {
-            store_out<sizeof(quad_t)>(dst, quad_t{e0, e1, e2, e3}, stream);
+            store_out<sizeof(quad_t)>(dst, P::store4(out[p][0], out[p][1], out[p][2], out[p][3]), stream);
           } else {
-            if (ok[0]) store_out<sizeof(elem_t)>(dst, e0, stream);
-            if (ok[1]) store_out<sizeof(elem_t)>(dst + sizeof(elem_t), e1, stream);
-            if (ok[2]) store_out<sizeof(elem_t)>(dst + 2 * sizeof(elem_t), e2, stream);
-            if (ok[3]) store_out<sizeof(elem_t)>(dst + 3 * sizeof(elem_t), e3, stream);
+            if (ok[0]) store_out<sizeof(elem_t)>(dst, P::store(out[p][0]), stream);
+            if (ok[1]) store_out<sizeof(elem_t)>(dst + sizeof(elem_t), P::store(out[p][1]), stream);
+            if (ok[2]) store_out<sizeof(elem_t)>(dst + 2 * sizeof(elem_t), P::store(out[p][2]), stream);
+            if (ok[3]) store_out<sizeof(elem_t)>(dst + 3 * sizeof(elem_t), P::store(out[p][3]), stream);
           }
         }
       }
@@ -181,20 +184,32 @@ void rcas_planar_geometry(int width, int height, int frames, bool overlapped, in
   *tiles_y = (height + r - 1) / r;
 }
 
+// RING by the launch: the shallow ring when it is short of waves, fewer than 6 per SIMD in 16-row strips (rcas_launch's rule).  8-bit
+// planes keep four rows in flight whatever the launch: packed, the deeper ring costs 4 registers (76 against 72, where fp16 pays 16),
+// and a single 4K frame, the launch the rule calls short, measured 27.9 us with it against 31.0.
+template <int FMT, bool EXACT, bool OPTS, bool WIDE>
+static void rcas_planar_launch_one(const RcasArgs& a, hipStream_t stream) {
+  const dim3 grid((unsigned)(a.tiles_x * a.tiles_y * a.frames)), block(kRcasPlanarThreads);
+  if constexpr (FMT != FSR1_FORMAT_RGB8_UNORM_PLANAR) {
+    if ((long long)a.tiles_x * ((a.in.height + 15) / 16) * a.frames * kRcasPlanarWaves < 6LL * 4 * 256) {
+      hipLaunchKernelGGL((rcas_planar_kernel<FMT, EXACT, OPTS, WIDE, 2>), grid, block, 0, stream, a);
+      return;
+    }
+  }
+  hipLaunchKernelGGL((rcas_planar_kernel<FMT, EXACT, OPTS, WIDE, 4>), grid, block, 0, stream, a);
+}
+
 // wide: the four-element accesses (the host has checked both images' base, pitch, plane and frame stride against them).
 hipError_t rcas_planar_launch(const RcasArgs& a, int fmt, bool exact, bool wide, hipStream_t stream) {
-  const dim3 grid((unsigned)(a.tiles_x * a.tiles_y * a.frames)), block(kRcasPlanarThreads);
   const bool opts = (a.flags & (FSR1_FLAG_RCAS_DENOISE | FSR1_FLAG_HDR_SQUARE)) != 0;
-  // shallow ring when the launch is short of waves: fewer than 6 per SIMD in 16-row strips (rcas_launch's rule)
-  const bool shallow = (long long)a.tiles_x * ((a.in.height + 15) / 16) * a.frames * kRcasPlanarWaves < 6LL * 4 * 256;
-#define FSR1_RCASP(F, E, O, V) do { if (shallow) hipLaunchKernelGGL((rcas_planar_kernel<F, E, O, V, 2>), grid, block, 0, stream, a); \
-                                    else hipLaunchKernelGGL((rcas_planar_kernel<F, E, O, V, 4>), grid, block, 0, stream, a); } while (0)
+#define FSR1_RCASP(F, E, O, V) rcas_planar_launch_one<F, E, O, V>(a, stream)
 #define FSR1_RCASP_V(F, E, O) do { if (wide) FSR1_RCASP(F, E, O, true); else FSR1_RCASP(F, E, O, false); } while (0)
 #define FSR1_RCASP_O(F, E) do { if (opts) FSR1_RCASP_V(F, E, true); else FSR1_RCASP_V(F, E, false); } while (0)
 #define FSR1_RCASP_E(F) do { if (exact) FSR1_RCASP_O(F, true); else FSR1_RCASP_O(F, false); } while (0)
   switch (fmt) {
     case FSR1_FORMAT_RGB16F_PLANAR: FSR1_RCASP_E(FSR1_FORMAT_RGB16F_PLANAR); break;
     case FSR1_FORMAT_RGB32F_PLANAR: FSR1_RCASP_E(FSR1_FORMAT_RGB32F_PLANAR); break;
+    case FSR1_FORMAT_RGB8_UNORM_PLANAR: FSR1_RCASP_E(FSR1_FORMAT_RGB8_UNORM_PLANAR); break;
     default: return hipErrorInvalidValue;
   }
 #undef FSR1_RCASP_E

@@ -1,4 +1,4 @@
-// Planar RGB storage (FSR1_FORMAT_RGB16F_PLANAR / FSR1_FORMAT_RGB32F_PLANAR) for the tiled forms: three planes R, G, B of
+// Planar RGB storage (FSR1_FORMAT_RGB16F_PLANAR / RGB32F_PLANAR / RGB8_UNORM_PLANAR) for the tiled forms: three planes R, G, B of
 // `height` rows each, rows `pitch` bytes apart, plane p of a frame at frame + p * pitch * height — a contiguous (N,3,H,W)
 // tensor, or one whose rows are padded.  The filters are the ones of fsr1_device_easu.hpp / fsr1_device_rcas.hpp on the same LDS
 // records and registers; what differs is the two ends that touch memory: this header holds the element types, the footprint
@@ -12,18 +12,45 @@
 
 namespace fsr1 {
 
+// load / store: an element to and from the filter's binary32.  V4: four adjacent columns of a plane row as one access; make4 builds
+// it from elements, get<I> reads column I, put<I> replaces it, store4 = make4 of four stored values.
 template <int FMT> struct Plane;  // FMT = a planar fsr1_format
 template <> struct Plane<FSR1_FORMAT_RGB16F_PLANAR> {
   typedef half_t E;                                                      // one element of a plane
   typedef half_t V2 __attribute__((ext_vector_type(2), aligned(4)));     // two / four adjacent columns of a plane row
   typedef half_t V4 __attribute__((ext_vector_type(4), aligned(8)));
+  static __device__ __forceinline__ float load(E e) { return (float)e; }
   static __device__ __forceinline__ E store(float x) { return (half_t)x; }  // RTNE, as Pixel<RGBA16F>::store
+  static __device__ __forceinline__ V4 make4(E a, E b, E c, E d) { return V4{a, b, c, d}; }
+  template <int I> static __device__ __forceinline__ E get(const V4& v) { return v[I]; }
+  template <int I> static __device__ __forceinline__ void put(V4& v, E e) { v[I] = e; }
+  static __device__ __forceinline__ V4 store4(float a, float b, float c, float d) { return V4{store(a), store(b), store(c), store(d)}; }
 };
 template <> struct Plane<FSR1_FORMAT_RGB32F_PLANAR> {
   typedef float E;
   typedef float V2 __attribute__((ext_vector_type(2), aligned(8)));
   typedef float V4 __attribute__((ext_vector_type(4), aligned(16)));
+  static __device__ __forceinline__ float load(E e) { return e; }
   static __device__ __forceinline__ E store(float x) { return x; }
+  static __device__ __forceinline__ V4 make4(E a, E b, E c, E d) { return V4{a, b, c, d}; }
+  template <int I> static __device__ __forceinline__ E get(const V4& v) { return v[I]; }
+  template <int I> static __device__ __forceinline__ void put(V4& v, E e) { v[I] = e; }
+  static __device__ __forceinline__ V4 store4(float a, float b, float c, float d) { return V4{a, b, c, d}; }
+};
+// 8-bit UNORM codes under the conversions pinned for RGBA8_UNORM (fsr1_hip.h).  Four columns are ONE dword, column I in byte I: a row
+// in flight costs a lane one register per plane, decoding column I is one v_cvt_f32_ubyteI and its two-instruction correction, and
+// four results are encoded and merged into the dword before the store.
+template <> struct Plane<FSR1_FORMAT_RGB8_UNORM_PLANAR> {
+  typedef uint8_t E;
+  typedef uint32_t V4;
+  static __device__ __forceinline__ float load(E e) { return unorm_decode<255>(e); }
+  static __device__ __forceinline__ E store(float x) { return (E)unorm_encode<255>(x); }
+  static __device__ __forceinline__ V4 make4(E a, E b, E c, E d) { return (V4)a | ((V4)b << 8) | ((V4)c << 16) | ((V4)d << 24); }
+  template <int I> static __device__ __forceinline__ E get(const V4& v) { return (E)(v >> (8 * I)); }
+  template <int I> static __device__ __forceinline__ void put(V4& v, E e) { v = (v & ~(0xffu << (8 * I))) | ((V4)e << (8 * I)); }
+  static __device__ __forceinline__ V4 store4(float a, float b, float c, float d) {  // (codes are <= 255: nothing to mask)
+    return unorm_encode<255>(a) | (unorm_encode<255>(b) << 8) | (unorm_encode<255>(c) << 16) | (unorm_encode<255>(d) << 24);
+  }
 };
 
 // bytes between the planes of a frame
@@ -42,7 +69,7 @@ __device__ __forceinline__ void easu_stage_footprint_planar(const EasuLds& l, co
   const int fw = FW ? FW : fw_rt, fh = FH ? FH : fh_rt;
   const long long ps = plane_stride(in);
   auto record = [](elem_t r, elem_t g, elem_t b) {
-    const float fr = (float)r, fg = (float)g, fb = (float)b;
+    const float fr = Plane<FMT>::load(r), fg = Plane<FMT>::load(g), fb = Plane<FMT>::load(b);
     return float4_t{fr, fg, fb, fmaf(fb, 0.5f, fmaf(fr, 0.5f, fg))};  // :363-366, as easu_stage_footprint
   };
   if (FW || fw <= 64) {
@@ -133,6 +160,50 @@ __device__ __forceinline__ void planar_store_quad_row(char* o, long long ps, rgb
     if (!row_in) return;
     if (xin0) planar_store1<FMT>(o, ps, left, streaming);
     if (xin1) planar_store1<FMT>(o + sizeof(elem_t), ps, right, streaming);
+  }
+}
+
+// The same row for 8-bit planes, where the aligned pair is only two bytes: the four-column form.  Each lane encodes its two pixels and
+// packs the codes (R | G << 8 | B << 16), takes the packed LEFT pixel of the lane to its right (one DPP move for the three channels)
+// and so holds its aligned pair {own right, neighbour's left}; two more moves hand the neighbour's pair on, and the EVEN quad columns
+// store one dword per plane — columns 64 tx + 2 qx .. + 3 of the row, a multiple of four — while the odd ones store nothing.  Quad
+// column 0 also stores its left pixel (the tile's first column) by itself; quad column 30 has only three columns left in the tile (the
+// fourth byte it was handed belongs to the next quad row) and stores them, like a dword cut by the image's right edge, byte by byte.
+// Every lane of the wave must make the call; `o` = address of the left pixel (column oxa, odd) in plane R, W = image width.
+// WIDE = false: the two pixels byte by byte.
+__device__ __forceinline__ uint32_t planar_codes(rgbf_t v) { return unorm_encode<255>(v.r) | (unorm_encode<255>(v.g) << 8) | (unorm_encode<255>(v.b) << 16); }
+__device__ __forceinline__ uint32_t dpp_shl1(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp((int)v, (int)v, kDppWaveShl1, 0xf, 0xf, false); }
+__device__ __forceinline__ void planar_store_codes(char* o, long long ps, uint32_t codes, bool streaming) {
+  store_out<1>(o, (uint8_t)codes, streaming);
+  store_out<1>(o + ps, (uint8_t)(codes >> 8), streaming);
+  store_out<1>(o + 2 * ps, (uint8_t)(codes >> 16), streaming);
+}
+template <bool WIDE>
+__device__ __forceinline__ void planar_store_quad_row_u8(char* o, long long ps, rgbf_t left, rgbf_t right, int qx, int oxa, int W, bool row_in,
+                                                         bool streaming) {
+  const uint32_t l = planar_codes(left), r = planar_codes(right);
+  if constexpr (WIDE) {
+    const uint32_t nl = dpp_shl1(l);                       // own pair = {r, nl}
+    const uint32_t nr = dpp_shl1(r), nnl = dpp_shl1(nl);  // the right neighbour's pair
+    if (!row_in || (qx & 1)) return;
+    if (qx == 0 && oxa >= 0) planar_store_codes(o, ps, l, streaming);
+    const int n = min(qx == 30 ? 3 : 4, W - (oxa + 1));  // columns oxa + 1 .. oxa + n are this lane's to store (n <= 0: none)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const uint32_t quad = ((r >> (8 * c)) & 0xffu) | (((nl >> (8 * c)) & 0xffu) << 8) | (((nr >> (8 * c)) & 0xffu) << 16) | ((nnl >> (8 * c)) << 24);
+      char* const p = o + 1 + c * ps;
+      if (n == 4) {
+        store_out<4>(p, quad, streaming);
+      } else {
+        if (n > 0) store_out<1>(p, (uint8_t)quad, streaming);
+        if (n > 1) store_out<1>(p + 1, (uint8_t)(quad >> 8), streaming);
+        if (n > 2) store_out<1>(p + 2, (uint8_t)(quad >> 16), streaming);
+      }
+    }
+  } else {
+    if (!row_in) return;
+    if (oxa >= 0 && oxa < W) planar_store_codes(o, ps, l, streaming);
+    if (oxa + 1 < W) planar_store_codes(o + 1, ps, r, streaming);
   }
 }
 

@@ -79,8 +79,10 @@ typedef enum fsr1_format {
   /* Planar RGB — what a PyTorch process holds: a contiguous (N,3,H,W) tensor, or one whose rows are padded.  No alpha.  A frame is
    * three planes R, G, B of `height` rows of `width` scalars each, rows row_pitch_bytes apart (0 = width x element size); plane p of
    * frame f starts at data + f * frame_stride_bytes + p * row_pitch_bytes * height; frame_stride_bytes 0 = 3 * pitch * height.
-   * Pointer, pitch and frame stride must be multiples of the ELEMENT size (2 or 4 bytes) and of nothing larger: where they are also
-   * multiples of 8 / 16 bytes the kernels move four columns of a plane row per access, otherwise element by element.
+   * Pointer, pitch and frame stride must be multiples of the ELEMENT size (1, 2 or 4 bytes) and of nothing larger: where they are also
+   * multiples of 4 / 8 / 16 bytes the kernels move four columns of a plane row per access, otherwise element by element.
+   * RGB8_UNORM_PLANAR holds 8-bit codes under the load / store rules pinned for RGBA8_UNORM above: every code is the one the
+   * RGBA8_UNORM kernels store for the same pixels with alpha 255, the 8-bit EASU -> RCAS intermediary included.
    * Accepted by fsr1_easu_dispatch, fsr1_rcas_dispatch, fsr1_upscale[_ex] / fsr1_upscale_plan / fsr1_pipeline_upscale without colour
    * stages (fused = 2 plans the two dispatches), in->format == out->format (and the intermediary's), with the F arithmetic: default or
    * FSR1_FLAG_MATH_EXACT; FSR1_FLAG_MATH_STRICT takes the EXACT kernels for both passes, as it does for RGBA32F (there is no strict
@@ -88,9 +90,10 @@ typedef enum fsr1_format {
    * images; every value is the one the interleaved kernels store for the same pixels with alpha 1.  FSR1_ERR_UNSUPPORTED (the message
    * says "planar"): FSR1_FLAG_MATH_PACKED_FP16, colour stages, row bands, the fused launches (fused = 1, or use_rcas without an
    * intermediary), FSR1_FLAG_RCAS_PASSTHROUGH_ALPHA (there is no alpha), and a planar image on one side with an interleaved one on
-   * the other. */
+   * the other, or a different planar format (there is no conversion between planar formats). */
   FSR1_FORMAT_RGB16F_PLANAR = 4,      /* binary16 planes, 6 B/pixel */
-  FSR1_FORMAT_RGB32F_PLANAR = 5       /* binary32 planes, 12 B/pixel */
+  FSR1_FORMAT_RGB32F_PLANAR = 5,      /* binary32 planes, 12 B/pixel */
+  FSR1_FORMAT_RGB8_UNORM_PLANAR = 6   /* 8-bit UNORM planes, 3 B/pixel */
 } fsr1_format;
 
 typedef struct fsr1_image {

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
-"""Planar RGB (FORMAT_RGB16F_PLANAR) against RGBA16F at 1920x1080 -> 3840x2160, default arithmetic, one frame per call.
+"""Planar RGB against its interleaved format at 1920x1080 -> 3840x2160, default arithmetic, one frame per call: FORMAT_RGB16F_PLANAR
+against RGBA16F, or (--dtype u8) FORMAT_RGB8_UNORM_PLANAR against RGBA8_UNORM.
 
   python tools/planar_bench.py --out profiles/planar_1080p_to_4k.json
+  python tools/planar_bench.py --dtype u8 --out profiles/planar_u8_1080p_to_4k.json
 
 Every configuration is timed between two events on the current stream over `--calls` back-to-back calls, seven windows per
 configuration with the configurations alternating; "cold" configurations walk a ring of buffer sets larger than the 256 MB
@@ -37,6 +39,7 @@ def main():
     ap.add_argument("--calls", type=int, default=300)
     ap.add_argument("--windows", type=int, default=7)
     ap.add_argument("--ring", type=int, default=8)
+    ap.add_argument("--dtype", choices=["f16", "u8"], default="f16")
     args = ap.parse_args()
     import torch
     fsr = importlib.import_module("fidelityfx-fsr_amd")
@@ -46,19 +49,24 @@ def main():
     iw, ih, ow, oh = 1920, 1080, 3840, 2160
     con, rcon = fsr.FsrEasuCon(iw, ih, iw, ih, ow, oh), fsr.FsrRcasCon(0.25)
     P = fsr.Planar
+    u8 = args.dtype == "u8"
+    tdt, inter = (torch.uint8, "rgba8") if u8 else (torch.float16, "rgba16f")
     rgba = torch.from_numpy(fsr.frames.synthetic_frame(iw, ih, k=0)).cuda()
+    if u8:  # the store rule of RGBA8_UNORM (include/fsr1_hip.h), alpha at its maximum
+        rgba = (rgba.float().clamp(0, 1) * 255 + 0.5).to(torch.uint8)
+        rgba[..., 3] = 255
     chw = rgba[..., :3].permute(2, 0, 1).contiguous()
 
     def ring(make):
         return [make() for _ in range(args.ring)]
 
-    z = lambda *s: torch.zeros(*s, dtype=torch.float16, device="cuda")  # noqa: E731
+    z = lambda *s: torch.zeros(*s, dtype=tdt, device="cuda")  # noqa: E731
     p_in, p_mid, p_out = ring(lambda: chw.clone()), ring(lambda: z(3, oh, ow)), ring(lambda: z(3, oh, ow))
     i_in, i_mid, i_out = ring(lambda: rgba.clone()), ring(lambda: z(oh, ow, 4)), ring(lambda: z(oh, ow, 4))
     for k in range(args.ring):  # real intermediaries for the RCAS-only configurations
         fsr.easu(P(p_in[k]), P(p_mid[k]), con=con)
         fsr.easu(i_in[k], i_mid[k], con=con)
-    ones = torch.ones(1, ih, iw, 1, dtype=torch.float16, device="cuda")
+    ones = torch.full((1, ih, iw, 1), 255 if u8 else 1, dtype=tdt, device="cuda")
 
     def wrapped(k):
         """What a caller of the interleaved ABI does for a (1,3,H,W) tensor today."""
@@ -77,14 +85,14 @@ def main():
 
     configs = {
         "rcas_planar_cold": (lambda k: fsr.rcas(P(p_mid[k]), P(p_out[k]), con=rcon), args.ring),
-        "rcas_rgba16f_cold": (lambda k: fsr.rcas(i_mid[k], i_out[k], con=rcon), args.ring),
+        "rcas_%s_cold" % inter: (lambda k: fsr.rcas(i_mid[k], i_out[k], con=rcon), args.ring),
         "rcas_planar_resident": (lambda k: fsr.rcas(P(p_mid[k]), P(p_out[k]), con=rcon), 1),
-        "rcas_rgba16f_resident": (lambda k: fsr.rcas(i_mid[k], i_out[k], con=rcon), 1),
+        "rcas_%s_resident" % inter: (lambda k: fsr.rcas(i_mid[k], i_out[k], con=rcon), 1),
         "easu_planar": (lambda k: fsr.easu(P(p_in[k]), P(p_mid[k]), con=con), args.ring),
-        "easu_rgba16f": (lambda k: fsr.easu(i_in[k], i_mid[k], con=con), args.ring),
+        "easu_%s" % inter: (lambda k: fsr.easu(i_in[k], i_mid[k], con=con), args.ring),
         "chain_planar": (chain_planar, args.ring),
-        "chain_rgba16f": (chain_rgba, args.ring),
-        "chain_rgba16f_permute_wrapped": (wrapped, args.ring),
+        "chain_%s" % inter: (chain_rgba, args.ring),
+        "chain_%s_permute_wrapped" % inter: (wrapped, args.ring),
     }
     # the planar chain and the wrapped interleaved chain compute the same image
     chain_planar(0)
@@ -104,9 +112,9 @@ def main():
             e1.synchronize()
             times[name].append(e0.elapsed_time(e1) * 1000.0 / args.calls)
     doc = {
-        "what": "planar RGB fp16 against RGBA16F, %dx%d -> %dx%d, default arithmetic, one frame per call; %d calls per window between two events on one "
+        "what": "planar RGB %s against %s, %dx%d -> %dx%d, default arithmetic, one frame per call; %d calls per window between two events on one "
                 "stream, %d windows per configuration, the configurations alternating; cold = a ring of %d buffer sets, resident = one set"
-                % (iw, ih, ow, oh, args.calls, args.windows, args.ring),
+                % ((("uint8", "RGBA8_UNORM") if u8 else ("fp16", "RGBA16F")) + (iw, ih, ow, oh, args.calls, args.windows, args.ring)),
         "device": torch.cuda.get_device_name(0),
         "clocks_and_power_after_the_run": smi(),
         "planar_chain_equals_permute_wrapped_chain": same,
