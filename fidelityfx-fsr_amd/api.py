@@ -21,6 +21,9 @@ FORMAT_R10G10B10A2_UNORM = 3
 FORMAT_RGB16F_PLANAR = 4  # three planes R, G, B: a (N,3,H,W) tensor, marked with Planar()
 FORMAT_RGB32F_PLANAR = 5
 FORMAT_RGB8_UNORM_PLANAR = 6  # uint8 planes: what a decoder hands over
+FORMAT_RGB16F = 8  # R, G, B interleaved, no alpha: a (N,H,W,3) or channels_last tensor, marked with Rgb()  (7 is unassigned)
+FORMAT_RGB32F = 9
+FORMAT_RGB8_UNORM = 10  # the (H,W,3) uint8 frame of a decoder or an OpenCV / PIL bridge
 
 FLAG_HDR_SQUARE = 1 << 0
 FLAG_RCAS_DENOISE = 1 << 1
@@ -127,14 +130,56 @@ class Planar:
         return Planar(torch.empty_like(self.t))
 
 
+class Rgb:
+    """Marks a CUDA tensor, float16, float32 or uint8, as packed 3-channel RGB without alpha (FORMAT_RGB16F / RGB32F / RGB8_UNORM):
+    shaped (H,W,3) or (N,H,W,3) — a decoder's frame, a model's last layer — or (N,3,H,W) in torch.channels_last memory format, which is
+    the same memory described the other way round.  Taken as it is: no pad to four channels, no slice afterwards.  Channels are one
+    element apart and pixels three; rows and frames may be padded.  Pass it wherever an image tensor goes (easu, rcas, FSR_Filter,
+    Pipeline.upscale); a bare tensor is always read as RGBA, so (H,W,3) without the marker is still refused."""
+
+    def __init__(self, t):
+        self.t = t
+
+    def image(self):
+        import torch
+        t = self.t
+        if not t.is_cuda:
+            raise Fsr1Error("image tensors must live on the GPU (got %s); there is no CPU path" % t.device)
+        if t.dim() == 3:
+            t = t.unsqueeze(0)
+        if t.dim() == 4 and t.shape[1] == 3 and t.stride(1) == 1 and (t.shape[-1] != 3 or t.stride(-1) != 1):
+            t = t.permute(0, 2, 3, 1)  # channels_last (N,3,H,W): the strides are checked below like any others
+        if t.dim() != 4 or t.shape[-1] != 3:
+            raise Fsr1Error("expected (N,H,W,3) or channels_last (N,3,H,W) RGB, got %s" % (tuple(self.t.shape),))
+        if t.dtype == torch.float16:
+            fmt, es = FORMAT_RGB16F, 2
+        elif t.dtype == torch.float32:
+            fmt, es = FORMAT_RGB32F, 4
+        elif t.dtype == torch.uint8:
+            fmt, es = FORMAT_RGB8_UNORM, 1
+        else:
+            raise Fsr1Error("3-channel images are float16, float32 or uint8, got %s" % t.dtype)
+        n, h, w, _ = t.shape
+        sn, sh, sw, sc = t.stride()
+        if sc != 1 or sw != 3:
+            raise Fsr1Error("pixels must be RGB-interleaved and dense along x (channel stride 1, pixel stride 3; got %d, %d)" % (sc, sw))
+        _check_strides(n, h, w, sn, sh, 3)
+        return fsr1_image(t.data_ptr(), w, h, fmt, n, sh * es, sn * es if n > 1 else 0)
+
+    def empty_like(self):
+        import torch
+        return Rgb(torch.empty_like(self.t))
+
+
 def image_of(t):
     """fsr1_image descriptor of a CUDA torch tensor:
       float16 / float32 / uint8, shaped (H,W,4) or (N,H,W,4)  -> RGBA16F / RGBA32F / RGBA8_UNORM
       int32, shaped (H,W) or (N,H,W)                          -> R10G10B10A2_UNORM (one packed word per pixel)
       Planar(float16 / float32 / uint8, shaped (3,H,W) or (N,3,H,W))  -> RGB16F_PLANAR / RGB32F_PLANAR / RGB8_UNORM_PLANAR
+      Rgb(float16 / float32 / uint8, shaped (H,W,3), (N,H,W,3) or channels_last (N,3,H,W))  -> RGB16F / RGB32F / RGB8_UNORM
     Row and frame strides are honoured; the innermost (x[, channel]) dims must be dense."""
     import torch
-    if isinstance(t, Planar):
+    if isinstance(t, (Planar, Rgb)):
         return t.image()
     if not t.is_cuda:
         raise Fsr1Error("image tensors must live on the GPU (got %s); there is no CPU path" % t.device)
@@ -385,7 +430,7 @@ class FSR_Filter:
         self._input, self._output, self._hdr = input, output, hdr
         # FSR_Filter.cpp:72-73 creates the EASU->RCAS intermediary at display size; here it has the
         # output's format (RGBA16F/RGBA32F) and batch size.
-        self.m_intermediary = None if self.fused is True else (output.empty_like() if isinstance(output, Planar) else torch.empty_like(output))
+        self.m_intermediary = None if self.fused is True else (output.empty_like() if isinstance(output, (Planar, Rgb)) else torch.empty_like(output))
 
     def OnDestroyWindowSizeDependentResources(self):
         self.m_intermediary = None

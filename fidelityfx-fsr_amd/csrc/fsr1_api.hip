@@ -46,6 +46,9 @@ void rcas_h_geometry(int fmt, int fout, int width, int height, int* tiles_x, int
 hipError_t easu_planar_launch(const EasuArgs& a, int fmt, bool exact, bool s2, bool wide, hipStream_t stream);
 hipError_t rcas_planar_launch(const RcasArgs& a, int fmt, bool exact, bool wide, hipStream_t stream);
 void rcas_planar_geometry(int width, int height, int frames, bool overlapped, int* tiles_x, int* tiles_y, int* rows);
+hipError_t easu_rgb_launch(const EasuArgs& a, int fmt, bool exact, bool s2, bool wide, hipStream_t stream);
+hipError_t rcas_rgb_launch(const RcasArgs& a, int fmt, bool exact, bool wide, hipStream_t stream);
+void rcas_rgb_geometry(int width, int height, int frames, bool overlapped, int* tiles_x, int* tiles_y, int* rows);
 }  // namespace fsr1
 
 using namespace fsr1;
@@ -135,8 +138,17 @@ static bool is_planar(int fmt) { return fmt == FSR1_FORMAT_RGB16F_PLANAR || fmt 
 static int image_planes(int fmt) { return is_planar(fmt) ? 3 : 1; }
 static bool any_planar(const fsr1_image* a, const fsr1_image* b) { return (a && is_planar(a->format)) || (b && is_planar(b->format)); }
 
+// Packed 3-channel RGB (R, G, B interleaved, no alpha, fsr1_hip.h): served like planar, by the plain EASU and RCAS dispatches in F
+// arithmetic; everything else refuses it with a message that says "3-channel".
+static bool is_rgb3(int fmt) { return fmt == FSR1_FORMAT_RGB16F || fmt == FSR1_FORMAT_RGB32F || fmt == FSR1_FORMAT_RGB8_UNORM; }
+static bool any_rgb3(const fsr1_image* a, const fsr1_image* b) { return (a && is_rgb3(a->format)) || (b && is_rgb3(b->format)); }
+static size_t rgb3_element_bytes(int fmt) { return fmt == FSR1_FORMAT_RGB32F ? 4 : (fmt == FSR1_FORMAT_RGB16F ? 2 : 1); }
+// (7 is unassigned: fsr1_hip.h)
+static bool format_known(int fmt) { return (fmt >= FSR1_FORMAT_RGBA16F && fmt <= FSR1_FORMAT_RGB8_UNORM_PLANAR) || is_rgb3(fmt); }
+
 // bytes of the unit rows are made of: an interleaved pixel, or one element of a plane
 static size_t pixel_bytes(int fmt) {
+  if (is_rgb3(fmt)) return 3 * rgb3_element_bytes(fmt);
   if (is_planar(fmt)) return fmt == FSR1_FORMAT_RGB32F_PLANAR ? 4 : (fmt == FSR1_FORMAT_RGB16F_PLANAR ? 2 : 1);
   return fmt == FSR1_FORMAT_RGBA32F ? 16 : (fmt == FSR1_FORMAT_RGBA16F ? 8 : 4);
 }
@@ -148,17 +160,18 @@ static int check_image(const fsr1_image* im, const char* name, ImageView* v) {
     return fail(FSR1_ERR_INVALID_ARGUMENT, "%s: bad extent %dx%dx%d", name, im->width, im->height, im->frames);
   if (im->width > (1 << 20) || im->height > (1 << 20))  // pixel coordinates stay exact in binary32 with room to spare
     return fail(FSR1_ERR_UNSUPPORTED, "%s: extent %dx%d beyond 2^20 pixels per side", name, im->width, im->height);
-  if (im->format < FSR1_FORMAT_RGBA16F || im->format > FSR1_FORMAT_RGB8_UNORM_PLANAR)
+  if (!format_known(im->format))
     return fail(FSR1_ERR_UNSUPPORTED, "%s: unsupported format %d", name, im->format);
   const size_t px = pixel_bytes(im->format);
+  const size_t al = is_rgb3(im->format) ? rgb3_element_bytes(im->format) : px;  // (a 3-channel pixel is aligned to its elements only)
   const long long pitch = im->row_pitch_bytes ? im->row_pitch_bytes : (long long)im->width * (long long)px;
-  if (pitch < (long long)im->width * (long long)px || pitch % (long long)px)
+  if (pitch < (long long)im->width * (long long)px || pitch % (long long)al)
     return fail(FSR1_ERR_INVALID_ARGUMENT, "%s: row pitch %lld too small or not a multiple of the pixel size", name, pitch);
   const long long frame_bytes = pitch * im->height * image_planes(im->format);  // (planar: the planes follow each other, pitch * height apart)
   const long long fstride = im->frame_stride_bytes ? im->frame_stride_bytes : frame_bytes;
   if (im->frames > 1 && fstride < frame_bytes)
     return fail(FSR1_ERR_INVALID_ARGUMENT, "%s: frame stride %lld smaller than one frame", name, fstride);
-  if (((uintptr_t)im->data % px) || (fstride % (long long)px))
+  if (((uintptr_t)im->data % al) || (fstride % (long long)al))
     return fail(FSR1_ERR_INVALID_ARGUMENT, "%s: data pointer / frame stride not aligned to the pixel size", name);
   v->base = static_cast<char*>(im->data);
   v->width = im->width;
@@ -250,6 +263,7 @@ static int check_color(const fsr1_color_stages* st, const char* who, ColorArgs* 
     int rc = check_image(st->noise, "noise", &nv);
     if (rc) return rc;
     if (is_planar(st->noise->format)) return fail(FSR1_ERR_UNSUPPORTED, "%s: a planar noise image is not supported", who);
+    if (is_rgb3(st->noise->format)) return fail(FSR1_ERR_UNSUPPORTED, "%s: a 3-channel noise image is not supported", who);
     const long long slice = (long long)(st->frame % (uint32_t)st->noise->frames);
     c->noise.base = nv.base + slice * nv.frame_stride;
     c->noise.width = nv.width;
@@ -387,6 +401,7 @@ int fsr1_easu_dispatch_band(const fsr1_image* in, const fsr1_image* out, const u
   if (origin_x < 0 || origin_y < 0 || origin_x > (1 << 20) || origin_y > (1 << 20))
     return fail(FSR1_ERR_INVALID_ARGUMENT, "easu band: origin (%d, %d) out of range", origin_x, origin_y);
   if (flags & FSR1_FLAG_MATH_PACKED_FP16) return fail(FSR1_ERR_UNSUPPORTED, "easu band: bands run with the F (binary32) arithmetic");
+  if (any_rgb3(in, out)) return fail(FSR1_ERR_UNSUPPORTED, "easu band: row bands are not built for 3-channel images");
   if (any_planar(in, out)) return fail(FSR1_ERR_UNSUPPORTED, "easu band: row bands are not built for planar images");
   return easu_dispatch_impl(in, out, con, flags, nullptr, origin_x, origin_y, stream);
 }
@@ -401,10 +416,24 @@ static int planar_refusals(const char* who, const fsr1_image* in, const fsr1_ima
   return FSR1_OK;
 }
 
-// EASU on planar images: `a` holds the checked views.  The interleaved dispatch's tile geometry without its tall-tile, F-strict and
-// pitched-LDS variants; FSR1_FLAG_MATH_STRICT takes the EXACT kernel (which is what it promises: EXACT's stored image).
+// What the 3-channel kernels (fsr1_easu_rgb.hip, fsr1_rcas_rgb.hip) do not serve, refused alike for both passes.
+static int rgb3_refusals(const char* who, const fsr1_image* in, const fsr1_image* out, uint32_t flags, bool have_stages) {
+  if (in->format != out->format)
+    return fail(FSR1_ERR_UNSUPPORTED, "%s: a 3-channel image on one side needs the same 3-channel format on the other (%d -> %d)", who, in->format, out->format);
+  if (flags & FSR1_FLAG_MATH_PACKED_FP16) return fail(FSR1_ERR_UNSUPPORTED, "%s: 3-channel images run with the F (binary32) arithmetic, not packed fp16", who);
+  if (have_stages) return fail(FSR1_ERR_UNSUPPORTED, "%s: colour stages are not built for 3-channel images", who);
+  if (flags & FSR1_FLAG_RCAS_PASSTHROUGH_ALPHA) return fail(FSR1_ERR_UNSUPPORTED, "%s: 3-channel images have no alpha to pass through", who);
+  return FSR1_OK;
+}
+
+// The 3-channel kernels take the four-element access (4 / 8 / 16 bytes) only where every address they form with it is aligned to it.
+static bool rgb3_wide(const fsr1_image* im, const ImageView& v) { return planar_aligned(im, v, 4 * rgb3_element_bytes(im->format)); }
+
+// EASU on planar and on 3-channel images: `a` holds the checked views.  The interleaved dispatch's tile geometry without its tall-tile,
+// F-strict and pitched-LDS variants; FSR1_FLAG_MATH_STRICT takes the EXACT kernel (which is what it promises: EXACT's stored image).
 static int easu_planar_dispatch(const fsr1_image* in, const fsr1_image* out, EasuArgs& a, const uint32_t con[16], uint32_t flags, void* stream) {
-  if (int rc = planar_refusals("easu", in, out, flags, a.color.stages != 0)) return rc;
+  const bool rgb3 = any_rgb3(in, out);
+  if (int rc = rgb3 ? rgb3_refusals("easu", in, out, flags, a.color.stages != 0) : planar_refusals("easu", in, out, flags, a.color.stages != 0)) return rc;
   if (!con) return fail(FSR1_ERR_INVALID_ARGUMENT, "easu: null constants");
   if (in->frames != out->frames) return fail(FSR1_ERR_INVALID_ARGUMENT, "easu: frame counts differ (%d vs %d)", in->frames, out->frames);
   if (overlaps(in, a.in, out, a.out)) return fail(FSR1_ERR_INVALID_ARGUMENT, "easu: input and output overlap");
@@ -427,7 +456,7 @@ static int easu_planar_dispatch(const fsr1_image* in, const fsr1_image* out, Eas
   a.tiles_x = (out->width + kTileW - 1) / kTileW;
   a.tiles_y = (out->height + kTileH - 1) / kTileH;
   a.frames = out->frames;
-  const bool beyond_cache = (unsigned long long)a.out.pitch * 3ull * (unsigned long long)out->height * (unsigned long long)out->frames > 2 * (unsigned long long)infinity_cache_bytes();
+  const bool beyond_cache = (unsigned long long)a.out.pitch * (unsigned long long)image_planes(out->format) * (unsigned long long)out->height * (unsigned long long)out->frames > 2 * (unsigned long long)infinity_cache_bytes();
   a.flags = resolve_output_policy(flags, beyond_cache);
   const bool s2 = con[0] == 0x3f000000u && con[1] == 0x3f000000u && con[2] == 0xbe800000u && con[3] == 0xbe800000u && !(flags & FSR1_FLAG_NO_FAST_PATHS);
   if (s2) {  // the shifted tiles of the exact-2x variant (easu_dispatch_impl)
@@ -438,8 +467,10 @@ static int easu_planar_dispatch(const fsr1_image* in, const fsr1_image* out, Eas
   }
   if (int rc = check_grid("easu", a.tiles_x, a.tiles_y, a.frames)) return rc;
   // the exact-2x variant's pair stores; 8-bit planes: its dword stores
-  const bool wide = planar_aligned(out, a.out, out->format == FSR1_FORMAT_RGB8_UNORM_PLANAR ? 4 : 2 * pixel_bytes(out->format));
-  const hipError_t e = easu_planar_launch(a, in->format, exact, s2, wide, static_cast<hipStream_t>(stream));
+  // (3-channel: its flat run of four-element stores)
+  const bool wide = rgb3 ? rgb3_wide(out, a.out) : planar_aligned(out, a.out, out->format == FSR1_FORMAT_RGB8_UNORM_PLANAR ? 4 : 2 * pixel_bytes(out->format));
+  const hipError_t e = rgb3 ? easu_rgb_launch(a, in->format, exact, s2, wide, static_cast<hipStream_t>(stream))
+                            : easu_planar_launch(a, in->format, exact, s2, wide, static_cast<hipStream_t>(stream));
   if (e != hipSuccess) return hip_fail(e, "easu launch");
   return FSR1_OK;
 }
@@ -454,7 +485,7 @@ static int easu_dispatch_impl(const fsr1_image* in, const fsr1_image* out, const
   if ((rc = check_image(in, "easu input", &a.in))) return rc;
   if ((rc = check_image(out, "easu output", &a.out))) return rc;
   if ((rc = check_color(stages, "easu", &a.color))) return rc;
-  if (any_planar(in, out)) return easu_planar_dispatch(in, out, a, con, flags, stream);
+  if (any_planar(in, out) || any_rgb3(in, out)) return easu_planar_dispatch(in, out, a, con, flags, stream);
   if (!con) return fail(FSR1_ERR_INVALID_ARGUMENT, "easu: null constants");
   if (a.color.stages ? !color_format_pair_ok(in->format, out->format) : in->format != out->format)
     return fail(FSR1_ERR_UNSUPPORTED, "easu: unsupported input/output format pair %d -> %d", in->format, out->format);
@@ -560,28 +591,36 @@ int fsr1_rcas_dispatch_band(const fsr1_image* in, const fsr1_image* out, const u
                             int32_t rows_below, void* stream) {
   if ((rows_above | rows_below) & ~1) return fail(FSR1_ERR_INVALID_ARGUMENT, "rcas band: rows_above / rows_below must be 0 or 1");
   if (flags & FSR1_FLAG_MATH_PACKED_FP16) return fail(FSR1_ERR_UNSUPPORTED, "rcas band: bands run with the F (binary32) arithmetic");
+  if (any_rgb3(in, out)) return fail(FSR1_ERR_UNSUPPORTED, "rcas band: row bands are not built for 3-channel images");
   if (any_planar(in, out)) return fail(FSR1_ERR_UNSUPPORTED, "rcas band: row bands are not built for planar images");
   return rcas_dispatch_impl(in, out, con, flags, nullptr, rows_above, rows_below, stream);
 }
 
 // RCAS on planar images: `a` holds the checked views.  F-strict's RCAS is the default arithmetic — but EASU has no strict variant on
 // planar storage and runs EXACT under the flag, and then RCAS does too (the rule of RGBA32F, fsr1_hip.h).
+// 3-channel images take the same road with their own strip kernel.
 static int rcas_planar_dispatch(const fsr1_image* in, const fsr1_image* out, RcasArgs& a, const uint32_t con[4], uint32_t flags, void* stream) {
-  if (int rc = planar_refusals("rcas", in, out, flags, a.color.stages != 0)) return rc;
+  const bool rgb3 = any_rgb3(in, out);
+  if (int rc = rgb3 ? rgb3_refusals("rcas", in, out, flags, a.color.stages != 0) : planar_refusals("rcas", in, out, flags, a.color.stages != 0)) return rc;
   if (!con) return fail(FSR1_ERR_INVALID_ARGUMENT, "rcas: null constants");
   if (in->width != out->width || in->height != out->height || in->frames != out->frames)
     return fail(FSR1_ERR_INVALID_ARGUMENT, "rcas: input %dx%dx%d and output %dx%dx%d extents differ", in->width, in->height,
                 in->frames, out->width, out->height, out->frames);
   if (overlaps(in, a.in, out, a.out)) return fail(FSR1_ERR_INVALID_ARGUMENT, "rcas: input and output overlap (RCAS cannot run in place)");
   memcpy(a.con, con, sizeof a.con);
-  rcas_planar_geometry(out->width, out->height, out->frames, (flags & FSR1_FLAG_FRAMES_OVERLAP) != 0, &a.tiles_x, &a.tiles_y, &a.rows);
+  (rgb3 ? rcas_rgb_geometry : rcas_planar_geometry)(out->width, out->height, out->frames, (flags & FSR1_FLAG_FRAMES_OVERLAP) != 0, &a.tiles_x, &a.tiles_y, &a.rows);
   a.frames = out->frames;
   if (int rc = check_grid("rcas", a.tiles_x, a.tiles_y, a.frames)) return rc;
-  a.flags = resolve_output_policy(flags, true);
+  // streaming stores by default, as the RGBA dispatch — except 3-channel binary16: a lane's three 8-byte stores each cover a third of
+  // every line of its run, and as non-temporal stores that took 41.5 us against 34.2 for plain ones on a 4K frame (uint8, dword stores:
+  // 30.7 streaming against 32.7 plain; binary32: unmeasured, keeps the streaming default) — DESIGN.md section 3.5b
+  a.flags = resolve_output_policy(flags, !(rgb3 && in->format == FSR1_FORMAT_RGB16F));
   a.rows_above = a.rows_below = 0;
-  const size_t access = 4 * pixel_bytes(in->format);  // a lane's four columns of a plane row
+  const size_t access = rgb3 ? 4 * rgb3_element_bytes(in->format) : 4 * pixel_bytes(in->format);  // a lane's four columns of a plane row / a third of its four pixels
   const bool wide = planar_aligned(in, a.in, access) && planar_aligned(out, a.out, access);
-  const hipError_t e = rcas_planar_launch(a, in->format, (flags & (FSR1_FLAG_MATH_EXACT | FSR1_FLAG_MATH_STRICT)) != 0, wide, static_cast<hipStream_t>(stream));
+  const bool exact = (flags & (FSR1_FLAG_MATH_EXACT | FSR1_FLAG_MATH_STRICT)) != 0;
+  const hipError_t e = rgb3 ? rcas_rgb_launch(a, in->format, exact, wide, static_cast<hipStream_t>(stream))
+                            : rcas_planar_launch(a, in->format, exact, wide, static_cast<hipStream_t>(stream));
   if (e != hipSuccess) return hip_fail(e, "rcas launch");
   return FSR1_OK;
 }
@@ -596,12 +635,12 @@ static int rcas_dispatch_impl(const fsr1_image* in, const fsr1_image* out, const
   // F-strict is EASU's property: RCAS runs the default arithmetic under it — except where EASU has no strict variant and runs EXACT
   // (RGBA32F storage, colour stages): then RCAS does too, so that the fused launch, which cannot mix arithmetics there, stays
   // bit-identical to the two dispatches (include/fsr1_hip.h)
-  if ((flags & FSR1_FLAG_MATH_STRICT) && !any_planar(in, out))
+  if ((flags & FSR1_FLAG_MATH_STRICT) && !any_planar(in, out) && !any_rgb3(in, out))
     flags = (flags & ~(uint32_t)FSR1_FLAG_MATH_STRICT) | ((in && (in->format == FSR1_FORMAT_RGBA32F || (stages && stages->stages))) ? (uint32_t)FSR1_FLAG_MATH_EXACT : 0u);
   if ((rc = check_image(in, "rcas input", &a.in))) return rc;
   if ((rc = check_image(out, "rcas output", &a.out))) return rc;
   if ((rc = check_color(stages, "rcas", &a.color))) return rc;
-  if (any_planar(in, out)) return rcas_planar_dispatch(in, out, a, con, flags, stream);
+  if (any_planar(in, out) || any_rgb3(in, out)) return rcas_planar_dispatch(in, out, a, con, flags, stream);
   if (!con) return fail(FSR1_ERR_INVALID_ARGUMENT, "rcas: null constants");
   if (a.color.stages ? !color_format_pair_ok(in->format, out->format) : in->format != out->format)
     return fail(FSR1_ERR_UNSUPPORTED, "rcas: unsupported input/output format pair %d -> %d", in->format, out->format);
@@ -677,6 +716,7 @@ static int fused_dispatch_impl(const fsr1_image* in, const fsr1_image* out, cons
   if ((rc = check_image(in, "fused input", &a.in))) return rc;
   if ((rc = check_image(out, "fused output", &a.out))) return rc;
   if ((rc = check_color(stages, "fused", &a.color))) return rc;
+  if (any_rgb3(in, out)) return fail(FSR1_ERR_UNSUPPORTED, "fused: the fused launches are not built for 3-channel images; run the EASU and RCAS dispatches");
   if (any_planar(in, out)) return fail(FSR1_ERR_UNSUPPORTED, "fused: the fused launches are not built for planar images; run the EASU and RCAS dispatches");
   if (!easu_con || !rcas_con) return fail(FSR1_ERR_INVALID_ARGUMENT, "fused: null constants");
   if (a.color.stages ? !color_format_pair_ok(in->format, out->format) : in->format != out->format)
@@ -750,6 +790,7 @@ int fsr1_color_dispatch(const fsr1_image* in, const fsr1_image* out, const fsr1_
   if ((rc = check_image(in, "color input", &a.in))) return rc;
   if ((rc = check_image(out, "color output", &a.out))) return rc;
   if ((rc = check_color(stages, "color", &a.color))) return rc;
+  if (any_rgb3(in, out)) return fail(FSR1_ERR_UNSUPPORTED, "color: colour stages are not built for 3-channel images");
   if (any_planar(in, out)) return fail(FSR1_ERR_UNSUPPORTED, "color: colour stages are not built for planar images");
   if (in->width != out->width || in->height != out->height || in->frames != out->frames)
     return fail(FSR1_ERR_INVALID_ARGUMENT, "color: input %dx%dx%d and output %dx%dx%d extents differ", in->width, in->height,
@@ -795,10 +836,16 @@ static int upscale_decide(const char* who, const fsr1_image* in, bool have_inter
   for (const fsr1_image* im : {in, out}) {
     if (im->width <= 0 || im->height <= 0 || im->frames <= 0)
       return fail(FSR1_ERR_INVALID_ARGUMENT, "%s: bad %s extent %dx%dx%d", who, im == in ? "input" : "output", im->width, im->height, im->frames);
-    if (im->format < FSR1_FORMAT_RGBA16F || im->format > FSR1_FORMAT_RGB8_UNORM_PLANAR)
+    if (!format_known(im->format))
       return fail(FSR1_ERR_UNSUPPORTED, "%s: unsupported %s format %d", who, im == in ? "input" : "output", im->format);
   }
-  const bool planar = any_planar(in, out);
+  const bool rgb3 = any_rgb3(in, out);
+  if (rgb3) {  // the same for 3-channel images (checked first: a 3-channel image beside a planar one is this refusal)
+    if (int rc = rgb3_refusals(who, in, out, p->flags, have_stages)) return rc;
+    if (p->use_rcas && (p->fused == 1 || !have_intermediary))
+      return fail(FSR1_ERR_UNSUPPORTED, "%s: 3-channel images run as two dispatches; pass an intermediary and fused = 0 or 2", who);
+  }
+  const bool planar = !rgb3 && any_planar(in, out);
   if (planar) {  // what the planar dispatches would refuse, and the fused launch they do not have — before anything is launched
     if (int rc = planar_refusals(who, in, out, p->flags, have_stages)) return rc;
     if (p->use_rcas && (p->fused == 1 || !have_intermediary))
@@ -851,7 +898,7 @@ static int upscale_decide(const char* who, const fsr1_image* in, bool have_inter
   // two dispatches — and where it could only mean the fused launch (no intermediary) the refusal is made here, not by a launch
   if (packed && have_stages && (p->fused == 1 || !have_intermediary))
     return fail(FSR1_ERR_UNSUPPORTED, "%s: the fused launch of packed-fp16 math runs without colour stages; pass an intermediary and fused = 0 or 2", who);
-  const bool fused = p->fused == 1 || (p->fused == 2 && !(packed && have_stages) && !planar &&
+  const bool fused = p->fused == 1 || (p->fused == 2 && !(packed && have_stages) && !planar && !rgb3 &&
                                        auto_takes_fused(in, have_intermediary, out, plan->easu_con, plan->math, have_stages));
   if (!fused && !have_intermediary) return fail(FSR1_ERR_INVALID_ARGUMENT, "%s: two-pass EASU+RCAS needs an intermediary image", who);
   if (fused) {  // the fused launch's own LDS bound (fused_dispatch_impl)
@@ -1051,11 +1098,12 @@ int fsr1_pipeline_upscale(fsr1_pipeline* p, const fsr1_image* in, const fsr1_ima
   fsr1_image mid_img;
   const fsr1_image* mid_p = nullptr;
   if (plan.pipeline == 0) {  // two dispatches: this slot's own intermediary, out's extent
-    // (planar: three planes, their rows padded to the RCAS kernel's 16-byte accesses whatever the width)
-    const size_t row = is_planar(mid_format) ? ((size_t)out->width * pixel_bytes(mid_format) + 15) & ~(size_t)15 : (size_t)out->width * pixel_bytes(mid_format);
+    // (planar: three planes, their rows padded to the RCAS kernel's 16-byte accesses whatever the width; 3-channel: the same padding)
+    const bool padded = is_planar(mid_format) || is_rgb3(mid_format);
+    const size_t row = padded ? ((size_t)out->width * pixel_bytes(mid_format) + 15) & ~(size_t)15 : (size_t)out->width * pixel_bytes(mid_format);
     const size_t need = row * (size_t)image_planes(mid_format) * (size_t)out->height * (size_t)out->frames;
     if (int rc = pipeline_grow(p, slot, need, "pipeline_upscale")) return rc;
-    mid_img = fsr1_image{p->mid[slot], out->width, out->height, mid_format, out->frames, is_planar(mid_format) ? (int64_t)row : 0, 0};
+    mid_img = fsr1_image{p->mid[slot], out->width, out->height, mid_format, out->frames, padded ? (int64_t)row : 0, 0};
     mid_p = &mid_img;
   }
   // (the plan is re-derived by fsr1_upscale_ex from the same arguments: `auto` with an intermediary on offer decides as it did above)

@@ -62,12 +62,14 @@ __device__ __forceinline__ long long plane_stride(const ImageView& v) { return v
 // and a wave issues the loads of all the rows of a trip before it converts the first.  Ends with a barrier.
 // FW, FH: compile-time footprint extent (the exact-2x tiles), 0 = run-time.  Footprints wider than a wave (minification) take a
 // linear walk.  All THREADS threads of the workgroup must make the call.
-template <int FMT, bool EXACT, int FW = 0, int FH = 0, int THREADS = 256>
+// PX: elements from one texel to the next in a row — 1 for planes; 3 for the packed 3-channel images of fsr1_device_rgb.hpp, whose
+// channels are then one element apart instead of a plane.
+template <int FMT, bool EXACT, int FW = 0, int FH = 0, int THREADS = 256, int PX = 1>
 __device__ __forceinline__ void easu_stage_footprint_planar(const EasuLds& l, const ImageView& in, const char* in_frame, int fx0, int fy0,
                                                             int fw_rt, int fh_rt, int tid) {
   typedef typename Plane<FMT>::E elem_t;
   const int fw = FW ? FW : fw_rt, fh = FH ? FH : fh_rt;
-  const long long ps = plane_stride(in);
+  const long long ps = PX == 1 ? plane_stride(in) : (long long)sizeof(elem_t);
   auto record = [](elem_t r, elem_t g, elem_t b) {
     const float fr = Plane<FMT>::load(r), fg = Plane<FMT>::load(g), fb = Plane<FMT>::load(b);
     return float4_t{fr, fg, fb, fmaf(fb, 0.5f, fmaf(fr, 0.5f, fg))};  // :363-366, as easu_stage_footprint
@@ -78,7 +80,7 @@ __device__ __forceinline__ void easu_stage_footprint_planar(const EasuLds& l, co
     constexpr int kU = FH ? (FH + kWaves - 1) / kWaves : 5;  // rows per wave and trip: 3 kU element loads in flight per lane
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const uint32_t xoff = (uint32_t)min(max(fx0 + lane, 0), in.width - 1) * (uint32_t)sizeof(elem_t);
+    const uint32_t xoff = (uint32_t)min(max(fx0 + lane, 0), in.width - 1) * (uint32_t)(PX * sizeof(elem_t));
     float4_t* const rec = l.tex + lane;
     if (lane < fw) {
 #pragma unroll 1
@@ -106,7 +108,7 @@ __device__ __forceinline__ void easu_stage_footprint_planar(const EasuLds& l, co
     for (int i = tid; i < n; i += THREADS) {
       const int ly = (int)(((float)i + 0.5f) * inv_fw);
       const int gy = min(max(fy0 + ly, 0), in.height - 1), gx = min(max(fx0 + (i - ly * fw), 0), in.width - 1);
-      const char* const p = in_frame + (long long)gy * in.pitch + (size_t)gx * sizeof(elem_t);
+      const char* const p = in_frame + (long long)gy * in.pitch + (size_t)gx * (PX * sizeof(elem_t));
       l.tex[i] = record(*reinterpret_cast<const elem_t*>(p), *reinterpret_cast<const elem_t*>(p + ps), *reinterpret_cast<const elem_t*>(p + 2 * ps));
     }
   }

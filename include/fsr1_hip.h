@@ -93,7 +93,26 @@ typedef enum fsr1_format {
    * the other, or a different planar format (there is no conversion between planar formats). */
   FSR1_FORMAT_RGB16F_PLANAR = 4,      /* binary16 planes, 6 B/pixel */
   FSR1_FORMAT_RGB32F_PLANAR = 5,      /* binary32 planes, 12 B/pixel */
-  FSR1_FORMAT_RGB8_UNORM_PLANAR = 6   /* 8-bit UNORM planes, 3 B/pixel */
+  FSR1_FORMAT_RGB8_UNORM_PLANAR = 6,  /* 8-bit UNORM planes, 3 B/pixel */
+  /* (7 is unassigned and stays FSR1_ERR_UNSUPPORTED: tests/test_abi.py probes it as the unknown format.)
+   *
+   * Packed 3-channel RGB: R, G, B interleaved with NO alpha, three elements per pixel — a (N,H,W,3) tensor, an (H,W,3) decoder
+   * frame, or a (N,3,H,W) tensor in channels_last memory format — taken as it is: no pad to four channels, no slice afterwards.
+   * Rows are row_pitch_bytes apart (0 = 3 * width * element size), frames frame_stride_bytes apart.  Pointer, pitch and frame stride
+   * must be multiples of the ELEMENT size (1, 2 or 4 bytes) and of nothing larger: where they are also multiples of 4 / 8 / 16 bytes
+   * (uint8 / binary16 / binary32) the kernels move four pixels as three accesses of that width, otherwise element by element.
+   * RGB8_UNORM holds 8-bit codes under RGBA8_UNORM's pinned load / store rules.  The contract is the planar formats': accepted by
+   * fsr1_easu_dispatch, fsr1_rcas_dispatch, fsr1_upscale[_ex] / fsr1_upscale_plan / fsr1_pipeline_upscale without colour stages
+   * (fused = 2 plans the two dispatches), in->format == out->format (and the intermediary's), default F arithmetic or
+   * FSR1_FLAG_MATH_EXACT; FSR1_FLAG_MATH_STRICT takes the EXACT kernels for both passes.  HDR_SQUARE, RCAS_DENOISE, the OUTPUT_* store
+   * policies and FRAMES_OVERLAP work as for RGBA; every stored value is the one the RGBA kernels of the same element type store for
+   * the same pixels with alpha 1 (uint8: 255), the uint8 EASU -> RCAS intermediary included.  FSR1_ERR_UNSUPPORTED (the message says
+   * "3-channel"): FSR1_FLAG_MATH_PACKED_FP16, colour stages and a 3-channel noise image, row bands, the fused launches (fused = 1, or
+   * use_rcas without an intermediary), FSR1_FLAG_RCAS_PASSTHROUGH_ALPHA, fsr1_color_dispatch, and a 3-channel image on one side with
+   * any other format on the other. */
+  FSR1_FORMAT_RGB16F = 8,             /* binary16, 6 B/pixel */
+  FSR1_FORMAT_RGB32F = 9,             /* binary32, 12 B/pixel */
+  FSR1_FORMAT_RGB8_UNORM = 10         /* 8-bit UNORM, 3 B/pixel */
 } fsr1_format;
 
 typedef struct fsr1_image {
