@@ -24,6 +24,9 @@ FORMAT_RGB8_UNORM_PLANAR = 6  # uint8 planes: what a decoder hands over
 FORMAT_RGB16F = 8  # R, G, B interleaved, no alpha: a (N,H,W,3) or channels_last tensor, marked with Rgb()  (7 is unassigned)
 FORMAT_RGB32F = 9
 FORMAT_RGB8_UNORM = 10  # the (H,W,3) uint8 frame of a decoder or an OpenCV / PIL bridge
+FORMAT_R16F = 11  # one channel (luma / greyscale): a (H,W), (N,H,W) or (N,1,H,W) tensor, marked with Mono()
+FORMAT_R32F = 12
+FORMAT_R8_UNORM = 13  # the Y plane of a decoded frame
 
 FLAG_HDR_SQUARE = 1 << 0
 FLAG_RCAS_DENOISE = 1 << 1
@@ -171,15 +174,57 @@ class Rgb:
         return Rgb(torch.empty_like(self.t))
 
 
+class Mono:
+    """Marks a CUDA tensor shaped (H,W), (N,H,W) or (N,1,H,W), float16, float32 or uint8, as single-channel (FORMAT_R16F / R32F /
+    R8_UNORM): the Y plane of a decoded frame, the tensor of a Y-channel model, greyscale imagery — taken as it is, no replication into
+    RGBA and no slice afterwards.  The result is channel R of FSR 1 on the image (L, L, L, 1).  Rows and frames may be padded; x must
+    be dense.  Pass it wherever an image tensor goes (easu, rcas, FSR_Filter, Pipeline.upscale); a bare int32 (N,H,W) tensor stays
+    R10G10B10A2."""
+
+    def __init__(self, t):
+        self.t = t
+
+    def image(self):
+        import torch
+        t = self.t
+        if not t.is_cuda:
+            raise Fsr1Error("image tensors must live on the GPU (got %s); there is no CPU path" % t.device)
+        if t.dim() == 4 and t.shape[1] == 1:
+            t = t[:, 0]
+        elif t.dim() == 2:
+            t = t.unsqueeze(0)
+        if t.dim() != 3:
+            raise Fsr1Error("expected (H,W), (N,H,W) or (N,1,H,W) single-channel, got %s" % (tuple(self.t.shape),))
+        if t.dtype == torch.float16:
+            fmt, es = FORMAT_R16F, 2
+        elif t.dtype == torch.float32:
+            fmt, es = FORMAT_R32F, 4
+        elif t.dtype == torch.uint8:
+            fmt, es = FORMAT_R8_UNORM, 1
+        else:
+            raise Fsr1Error("single-channel images are float16, float32 or uint8, got %s" % t.dtype)
+        n, h, w = t.shape
+        sn, sh, sw = t.stride()
+        if sw != 1:
+            raise Fsr1Error("single-channel images must be dense along x (got a stride of %d elements)" % sw)
+        _check_strides(n, h, w, sn, sh, 1)
+        return fsr1_image(t.data_ptr(), w, h, fmt, n, sh * es, sn * es if n > 1 else 0)
+
+    def empty_like(self):
+        import torch
+        return Mono(torch.empty_like(self.t))
+
+
 def image_of(t):
     """fsr1_image descriptor of a CUDA torch tensor:
       float16 / float32 / uint8, shaped (H,W,4) or (N,H,W,4)  -> RGBA16F / RGBA32F / RGBA8_UNORM
       int32, shaped (H,W) or (N,H,W)                          -> R10G10B10A2_UNORM (one packed word per pixel)
       Planar(float16 / float32 / uint8, shaped (3,H,W) or (N,3,H,W))  -> RGB16F_PLANAR / RGB32F_PLANAR / RGB8_UNORM_PLANAR
       Rgb(float16 / float32 / uint8, shaped (H,W,3), (N,H,W,3) or channels_last (N,3,H,W))  -> RGB16F / RGB32F / RGB8_UNORM
+      Mono(float16 / float32 / uint8, shaped (H,W), (N,H,W) or (N,1,H,W))  -> R16F / R32F / R8_UNORM
     Row and frame strides are honoured; the innermost (x[, channel]) dims must be dense."""
     import torch
-    if isinstance(t, (Planar, Rgb)):
+    if isinstance(t, (Planar, Rgb, Mono)):
         return t.image()
     if not t.is_cuda:
         raise Fsr1Error("image tensors must live on the GPU (got %s); there is no CPU path" % t.device)
@@ -430,7 +475,7 @@ class FSR_Filter:
         self._input, self._output, self._hdr = input, output, hdr
         # FSR_Filter.cpp:72-73 creates the EASU->RCAS intermediary at display size; here it has the
         # output's format (RGBA16F/RGBA32F) and batch size.
-        self.m_intermediary = None if self.fused is True else (output.empty_like() if isinstance(output, (Planar, Rgb)) else torch.empty_like(output))
+        self.m_intermediary = None if self.fused is True else (output.empty_like() if isinstance(output, (Planar, Rgb, Mono)) else torch.empty_like(output))
 
     def OnDestroyWindowSizeDependentResources(self):
         self.m_intermediary = None

@@ -49,6 +49,11 @@ void rcas_planar_geometry(int width, int height, int frames, bool overlapped, in
 hipError_t easu_rgb_launch(const EasuArgs& a, int fmt, bool exact, bool s2, bool wide, hipStream_t stream);
 hipError_t rcas_rgb_launch(const RcasArgs& a, int fmt, bool exact, bool wide, hipStream_t stream);
 void rcas_rgb_geometry(int width, int height, int frames, bool overlapped, int* tiles_x, int* tiles_y, int* rows);
+hipError_t easu_mono_launch(const EasuArgs& a, int fmt, bool exact, bool s2, bool wide, hipStream_t stream);
+size_t easu_mono_lds_bytes(int fp_w, int fp_h);
+hipError_t rcas_mono_launch(const RcasArgs& a, int fmt, bool exact, bool wide, hipStream_t stream);
+void rcas_mono_geometry(int fmt, int width, int height, int frames, bool overlapped, int cus, int* tiles_x, int* tiles_y, int* rows);
+size_t rcas_mono_access_bytes(int fmt);
 }  // namespace fsr1
 
 using namespace fsr1;
@@ -143,12 +148,17 @@ static bool any_planar(const fsr1_image* a, const fsr1_image* b) { return (a && 
 static bool is_rgb3(int fmt) { return fmt == FSR1_FORMAT_RGB16F || fmt == FSR1_FORMAT_RGB32F || fmt == FSR1_FORMAT_RGB8_UNORM; }
 static bool any_rgb3(const fsr1_image* a, const fsr1_image* b) { return (a && is_rgb3(a->format)) || (b && is_rgb3(b->format)); }
 static size_t rgb3_element_bytes(int fmt) { return fmt == FSR1_FORMAT_RGB32F ? 4 : (fmt == FSR1_FORMAT_RGB16F ? 2 : 1); }
+// Single-channel images (one plane, fsr1_hip.h): served like planar, by the plain EASU and RCAS dispatches in F arithmetic, with
+// kernels of their own (fsr1_easu_mono.hip, fsr1_rcas_mono.hip); everything else refuses them with a message that says "single-channel".
+static bool is_mono(int fmt) { return fmt == FSR1_FORMAT_R16F || fmt == FSR1_FORMAT_R32F || fmt == FSR1_FORMAT_R8_UNORM; }
+static bool any_mono(const fsr1_image* a, const fsr1_image* b) { return (a && is_mono(a->format)) || (b && is_mono(b->format)); }
 // (7 is unassigned: fsr1_hip.h)
-static bool format_known(int fmt) { return (fmt >= FSR1_FORMAT_RGBA16F && fmt <= FSR1_FORMAT_RGB8_UNORM_PLANAR) || is_rgb3(fmt); }
+static bool format_known(int fmt) { return (fmt >= FSR1_FORMAT_RGBA16F && fmt <= FSR1_FORMAT_RGB8_UNORM_PLANAR) || is_rgb3(fmt) || is_mono(fmt); }
 
 // bytes of the unit rows are made of: an interleaved pixel, or one element of a plane
 static size_t pixel_bytes(int fmt) {
   if (is_rgb3(fmt)) return 3 * rgb3_element_bytes(fmt);
+  if (is_mono(fmt)) return fmt == FSR1_FORMAT_R32F ? 4 : (fmt == FSR1_FORMAT_R16F ? 2 : 1);
   if (is_planar(fmt)) return fmt == FSR1_FORMAT_RGB32F_PLANAR ? 4 : (fmt == FSR1_FORMAT_RGB16F_PLANAR ? 2 : 1);
   return fmt == FSR1_FORMAT_RGBA32F ? 16 : (fmt == FSR1_FORMAT_RGBA16F ? 8 : 4);
 }
@@ -264,6 +274,7 @@ static int check_color(const fsr1_color_stages* st, const char* who, ColorArgs* 
     if (rc) return rc;
     if (is_planar(st->noise->format)) return fail(FSR1_ERR_UNSUPPORTED, "%s: a planar noise image is not supported", who);
     if (is_rgb3(st->noise->format)) return fail(FSR1_ERR_UNSUPPORTED, "%s: a 3-channel noise image is not supported", who);
+    if (is_mono(st->noise->format)) return fail(FSR1_ERR_UNSUPPORTED, "%s: a single-channel noise image is not supported", who);
     const long long slice = (long long)(st->frame % (uint32_t)st->noise->frames);
     c->noise.base = nv.base + slice * nv.frame_stride;
     c->noise.width = nv.width;
@@ -282,6 +293,9 @@ static int check_color(const fsr1_color_stages* st, const char* who, ColorArgs* 
 static bool color_format_pair_ok(int fin, int fout) {
   return fin == fout || (fin == FSR1_FORMAT_RGBA16F && (fout == FSR1_FORMAT_RGBA8_UNORM || fout == FSR1_FORMAT_R10G10B10A2_UNORM));
 }
+
+// LDS bytes of a tile's staged footprint: a value + an analysis record per texel for single-channel images, the RGBA record otherwise
+static size_t easu_footprint_lds_bytes(int fmt, int fp_w, int fp_h) { return is_mono(fmt) ? easu_mono_lds_bytes(fp_w, fp_h) : easu_lds_bytes(fmt, fp_w, fp_h); }
 
 // Planar kernels take an access of `bytes` only where every address they form with it is aligned to it: base, pitch and (batches)
 // frame stride are multiples — and with them the plane stride pitch * height.
@@ -401,6 +415,7 @@ int fsr1_easu_dispatch_band(const fsr1_image* in, const fsr1_image* out, const u
   if (origin_x < 0 || origin_y < 0 || origin_x > (1 << 20) || origin_y > (1 << 20))
     return fail(FSR1_ERR_INVALID_ARGUMENT, "easu band: origin (%d, %d) out of range", origin_x, origin_y);
   if (flags & FSR1_FLAG_MATH_PACKED_FP16) return fail(FSR1_ERR_UNSUPPORTED, "easu band: bands run with the F (binary32) arithmetic");
+  if (any_mono(in, out)) return fail(FSR1_ERR_UNSUPPORTED, "easu band: row bands are not built for single-channel images");
   if (any_rgb3(in, out)) return fail(FSR1_ERR_UNSUPPORTED, "easu band: row bands are not built for 3-channel images");
   if (any_planar(in, out)) return fail(FSR1_ERR_UNSUPPORTED, "easu band: row bands are not built for planar images");
   return easu_dispatch_impl(in, out, con, flags, nullptr, origin_x, origin_y, stream);
@@ -426,14 +441,26 @@ static int rgb3_refusals(const char* who, const fsr1_image* in, const fsr1_image
   return FSR1_OK;
 }
 
+// What the single-channel kernels (fsr1_easu_mono.hip, fsr1_rcas_mono.hip) do not serve, refused alike for both passes.
+static int mono_refusals(const char* who, const fsr1_image* in, const fsr1_image* out, uint32_t flags, bool have_stages) {
+  if (in->format != out->format)
+    return fail(FSR1_ERR_UNSUPPORTED, "%s: a single-channel image on one side needs the same single-channel format on the other (%d -> %d)", who, in->format, out->format);
+  if (flags & FSR1_FLAG_MATH_PACKED_FP16) return fail(FSR1_ERR_UNSUPPORTED, "%s: single-channel images run with the F (binary32) arithmetic, not packed fp16", who);
+  if (have_stages) return fail(FSR1_ERR_UNSUPPORTED, "%s: colour stages are not built for single-channel images", who);
+  if (flags & FSR1_FLAG_RCAS_PASSTHROUGH_ALPHA) return fail(FSR1_ERR_UNSUPPORTED, "%s: single-channel images have no alpha to pass through", who);
+  return FSR1_OK;
+}
+
 // The 3-channel kernels take the four-element access (4 / 8 / 16 bytes) only where every address they form with it is aligned to it.
 static bool rgb3_wide(const fsr1_image* im, const ImageView& v) { return planar_aligned(im, v, 4 * rgb3_element_bytes(im->format)); }
 
 // EASU on planar and on 3-channel images: `a` holds the checked views.  The interleaved dispatch's tile geometry without its tall-tile,
 // F-strict and pitched-LDS variants; FSR1_FLAG_MATH_STRICT takes the EXACT kernel (which is what it promises: EXACT's stored image).
+// Single-channel images take the same road with their own kernel and its smaller LDS footprint.
 static int easu_planar_dispatch(const fsr1_image* in, const fsr1_image* out, EasuArgs& a, const uint32_t con[16], uint32_t flags, void* stream) {
-  const bool rgb3 = any_rgb3(in, out);
-  if (int rc = rgb3 ? rgb3_refusals("easu", in, out, flags, a.color.stages != 0) : planar_refusals("easu", in, out, flags, a.color.stages != 0)) return rc;
+  const bool mono = any_mono(in, out), rgb3 = !mono && any_rgb3(in, out);
+  if (int rc = mono ? mono_refusals("easu", in, out, flags, a.color.stages != 0)
+               : rgb3 ? rgb3_refusals("easu", in, out, flags, a.color.stages != 0) : planar_refusals("easu", in, out, flags, a.color.stages != 0)) return rc;
   if (!con) return fail(FSR1_ERR_INVALID_ARGUMENT, "easu: null constants");
   if (in->frames != out->frames) return fail(FSR1_ERR_INVALID_ARGUMENT, "easu: frame counts differ (%d vs %d)", in->frames, out->frames);
   if (overlaps(in, a.in, out, a.out)) return fail(FSR1_ERR_INVALID_ARGUMENT, "easu: input and output overlap");
@@ -448,7 +475,7 @@ static int easu_planar_dispatch(const fsr1_image* in, const fsr1_image* out, Eas
   a.fp_w = footprint_extent(out->width, kTileW, 0, sx, bx);
   a.fp_h = footprint_extent(out->height, kTileH, 0, sy, by);
   if (a.fp_w < 0 || a.fp_h < 0) return fail(FSR1_ERR_INVALID_ARGUMENT, "easu: scale constants con0.xy = (%g, %g) are not usable", sx, sy);
-  if (easu_lds_bytes(in->format, a.fp_w, a.fp_h) > device_lds_per_cu())
+  if (easu_footprint_lds_bytes(in->format, a.fp_w, a.fp_h) > device_lds_per_cu())
     return fail(FSR1_ERR_UNSUPPORTED, "easu: input/output ratio (%g, %g) needs a %dx%d texel footprint per tile, beyond the LDS budget "
                                       "(EASU is an upscaler; ratios up to ~3x minification are supported)", sx, sy, a.fp_w, a.fp_h);
   if ((long long)(a.fp_h + 1) * a.in.pitch >= (1ll << 31))
@@ -467,10 +494,12 @@ static int easu_planar_dispatch(const fsr1_image* in, const fsr1_image* out, Eas
   }
   if (int rc = check_grid("easu", a.tiles_x, a.tiles_y, a.frames)) return rc;
   // the exact-2x variant's pair stores; 8-bit planes: its dword stores
-  // (3-channel: its flat run of four-element stores)
-  const bool wide = rgb3 ? rgb3_wide(out, a.out) : planar_aligned(out, a.out, out->format == FSR1_FORMAT_RGB8_UNORM_PLANAR ? 4 : 2 * pixel_bytes(out->format));
-  const hipError_t e = rgb3 ? easu_rgb_launch(a, in->format, exact, s2, wide, static_cast<hipStream_t>(stream))
-                            : easu_planar_launch(a, in->format, exact, s2, wide, static_cast<hipStream_t>(stream));
+  // (3-channel: its flat run of four-element stores; single-channel: pairs and dwords like planar's)
+  const bool u8 = out->format == FSR1_FORMAT_RGB8_UNORM_PLANAR || out->format == FSR1_FORMAT_R8_UNORM;
+  const bool wide = rgb3 ? rgb3_wide(out, a.out) : planar_aligned(out, a.out, u8 ? 4 : 2 * pixel_bytes(out->format));
+  const hipError_t e = mono   ? easu_mono_launch(a, in->format, exact, s2, wide, static_cast<hipStream_t>(stream))
+                       : rgb3 ? easu_rgb_launch(a, in->format, exact, s2, wide, static_cast<hipStream_t>(stream))
+                              : easu_planar_launch(a, in->format, exact, s2, wide, static_cast<hipStream_t>(stream));
   if (e != hipSuccess) return hip_fail(e, "easu launch");
   return FSR1_OK;
 }
@@ -485,7 +514,7 @@ static int easu_dispatch_impl(const fsr1_image* in, const fsr1_image* out, const
   if ((rc = check_image(in, "easu input", &a.in))) return rc;
   if ((rc = check_image(out, "easu output", &a.out))) return rc;
   if ((rc = check_color(stages, "easu", &a.color))) return rc;
-  if (any_planar(in, out) || any_rgb3(in, out)) return easu_planar_dispatch(in, out, a, con, flags, stream);
+  if (any_planar(in, out) || any_rgb3(in, out) || any_mono(in, out)) return easu_planar_dispatch(in, out, a, con, flags, stream);
   if (!con) return fail(FSR1_ERR_INVALID_ARGUMENT, "easu: null constants");
   if (a.color.stages ? !color_format_pair_ok(in->format, out->format) : in->format != out->format)
     return fail(FSR1_ERR_UNSUPPORTED, "easu: unsupported input/output format pair %d -> %d", in->format, out->format);
@@ -591,6 +620,7 @@ int fsr1_rcas_dispatch_band(const fsr1_image* in, const fsr1_image* out, const u
                             int32_t rows_below, void* stream) {
   if ((rows_above | rows_below) & ~1) return fail(FSR1_ERR_INVALID_ARGUMENT, "rcas band: rows_above / rows_below must be 0 or 1");
   if (flags & FSR1_FLAG_MATH_PACKED_FP16) return fail(FSR1_ERR_UNSUPPORTED, "rcas band: bands run with the F (binary32) arithmetic");
+  if (any_mono(in, out)) return fail(FSR1_ERR_UNSUPPORTED, "rcas band: row bands are not built for single-channel images");
   if (any_rgb3(in, out)) return fail(FSR1_ERR_UNSUPPORTED, "rcas band: row bands are not built for 3-channel images");
   if (any_planar(in, out)) return fail(FSR1_ERR_UNSUPPORTED, "rcas band: row bands are not built for planar images");
   return rcas_dispatch_impl(in, out, con, flags, nullptr, rows_above, rows_below, stream);
@@ -625,6 +655,27 @@ static int rcas_planar_dispatch(const fsr1_image* in, const fsr1_image* out, Rca
   return FSR1_OK;
 }
 
+// RCAS on single-channel images: `a` holds the checked views.  The lanes' groups move as one access where both images' base, pitch
+// and frame stride are multiples of it, element by element otherwise; EXACT under FSR1_FLAG_MATH_STRICT, as for planar storage.
+static int rcas_mono_dispatch(const fsr1_image* in, const fsr1_image* out, RcasArgs& a, const uint32_t con[4], uint32_t flags, void* stream) {
+  if (int rc = mono_refusals("rcas", in, out, flags, a.color.stages != 0)) return rc;
+  if (!con) return fail(FSR1_ERR_INVALID_ARGUMENT, "rcas: null constants");
+  if (in->width != out->width || in->height != out->height || in->frames != out->frames)
+    return fail(FSR1_ERR_INVALID_ARGUMENT, "rcas: input %dx%dx%d and output %dx%dx%d extents differ", in->width, in->height,
+                in->frames, out->width, out->height, out->frames);
+  if (overlaps(in, a.in, out, a.out)) return fail(FSR1_ERR_INVALID_ARGUMENT, "rcas: input and output overlap (RCAS cannot run in place)");
+  memcpy(a.con, con, sizeof a.con);
+  rcas_mono_geometry(in->format, out->width, out->height, out->frames, (flags & FSR1_FLAG_FRAMES_OVERLAP) != 0, device_cus(), &a.tiles_x, &a.tiles_y, &a.rows);
+  a.frames = out->frames;
+  if (int rc = check_grid("rcas", a.tiles_x, a.tiles_y, a.frames)) return rc;
+  a.flags = resolve_output_policy(flags, true);
+  a.rows_above = a.rows_below = 0;
+  const bool exact = (flags & (FSR1_FLAG_MATH_EXACT | FSR1_FLAG_MATH_STRICT)) != 0;
+  const bool wide = planar_aligned(in, a.in, rcas_mono_access_bytes(in->format)) && planar_aligned(out, a.out, rcas_mono_access_bytes(in->format));
+  if (const hipError_t e = rcas_mono_launch(a, in->format, exact, wide, static_cast<hipStream_t>(stream)); e != hipSuccess) return hip_fail(e, "rcas launch");
+  return FSR1_OK;
+}
+
 static int rcas_dispatch_impl(const fsr1_image* in, const fsr1_image* out, const uint32_t con[4], uint32_t flags,
                               const fsr1_color_stages* stages, int rows_above, int rows_below, void* stream) {
   const Range range("rcas", in, out);
@@ -635,11 +686,12 @@ static int rcas_dispatch_impl(const fsr1_image* in, const fsr1_image* out, const
   // F-strict is EASU's property: RCAS runs the default arithmetic under it — except where EASU has no strict variant and runs EXACT
   // (RGBA32F storage, colour stages): then RCAS does too, so that the fused launch, which cannot mix arithmetics there, stays
   // bit-identical to the two dispatches (include/fsr1_hip.h)
-  if ((flags & FSR1_FLAG_MATH_STRICT) && !any_planar(in, out) && !any_rgb3(in, out))
+  if ((flags & FSR1_FLAG_MATH_STRICT) && !any_planar(in, out) && !any_rgb3(in, out) && !any_mono(in, out))
     flags = (flags & ~(uint32_t)FSR1_FLAG_MATH_STRICT) | ((in && (in->format == FSR1_FORMAT_RGBA32F || (stages && stages->stages))) ? (uint32_t)FSR1_FLAG_MATH_EXACT : 0u);
   if ((rc = check_image(in, "rcas input", &a.in))) return rc;
   if ((rc = check_image(out, "rcas output", &a.out))) return rc;
   if ((rc = check_color(stages, "rcas", &a.color))) return rc;
+  if (any_mono(in, out)) return rcas_mono_dispatch(in, out, a, con, flags, stream);
   if (any_planar(in, out) || any_rgb3(in, out)) return rcas_planar_dispatch(in, out, a, con, flags, stream);
   if (!con) return fail(FSR1_ERR_INVALID_ARGUMENT, "rcas: null constants");
   if (a.color.stages ? !color_format_pair_ok(in->format, out->format) : in->format != out->format)
@@ -716,6 +768,7 @@ static int fused_dispatch_impl(const fsr1_image* in, const fsr1_image* out, cons
   if ((rc = check_image(in, "fused input", &a.in))) return rc;
   if ((rc = check_image(out, "fused output", &a.out))) return rc;
   if ((rc = check_color(stages, "fused", &a.color))) return rc;
+  if (any_mono(in, out)) return fail(FSR1_ERR_UNSUPPORTED, "fused: the fused launches are not built for single-channel images; run the EASU and RCAS dispatches");
   if (any_rgb3(in, out)) return fail(FSR1_ERR_UNSUPPORTED, "fused: the fused launches are not built for 3-channel images; run the EASU and RCAS dispatches");
   if (any_planar(in, out)) return fail(FSR1_ERR_UNSUPPORTED, "fused: the fused launches are not built for planar images; run the EASU and RCAS dispatches");
   if (!easu_con || !rcas_con) return fail(FSR1_ERR_INVALID_ARGUMENT, "fused: null constants");
@@ -790,6 +843,7 @@ int fsr1_color_dispatch(const fsr1_image* in, const fsr1_image* out, const fsr1_
   if ((rc = check_image(in, "color input", &a.in))) return rc;
   if ((rc = check_image(out, "color output", &a.out))) return rc;
   if ((rc = check_color(stages, "color", &a.color))) return rc;
+  if (any_mono(in, out)) return fail(FSR1_ERR_UNSUPPORTED, "color: colour stages are not built for single-channel images");
   if (any_rgb3(in, out)) return fail(FSR1_ERR_UNSUPPORTED, "color: colour stages are not built for 3-channel images");
   if (any_planar(in, out)) return fail(FSR1_ERR_UNSUPPORTED, "color: colour stages are not built for planar images");
   if (in->width != out->width || in->height != out->height || in->frames != out->frames)
@@ -839,13 +893,19 @@ static int upscale_decide(const char* who, const fsr1_image* in, bool have_inter
     if (!format_known(im->format))
       return fail(FSR1_ERR_UNSUPPORTED, "%s: unsupported %s format %d", who, im == in ? "input" : "output", im->format);
   }
-  const bool rgb3 = any_rgb3(in, out);
-  if (rgb3) {  // the same for 3-channel images (checked first: a 3-channel image beside a planar one is this refusal)
+  const bool mono = any_mono(in, out);
+  if (mono) {  // single-channel images (checked first: a single-channel image beside any other format is this refusal)
+    if (int rc = mono_refusals(who, in, out, p->flags, have_stages)) return rc;
+    if (p->use_rcas && (p->fused == 1 || !have_intermediary))
+      return fail(FSR1_ERR_UNSUPPORTED, "%s: single-channel images run as two dispatches; pass an intermediary and fused = 0 or 2", who);
+  }
+  const bool rgb3 = !mono && any_rgb3(in, out);
+  if (rgb3) {  // the same for 3-channel images (checked before planar: a 3-channel image beside a planar one is this refusal)
     if (int rc = rgb3_refusals(who, in, out, p->flags, have_stages)) return rc;
     if (p->use_rcas && (p->fused == 1 || !have_intermediary))
       return fail(FSR1_ERR_UNSUPPORTED, "%s: 3-channel images run as two dispatches; pass an intermediary and fused = 0 or 2", who);
   }
-  const bool planar = !rgb3 && any_planar(in, out);
+  const bool planar = !mono && !rgb3 && any_planar(in, out);
   if (planar) {  // what the planar dispatches would refuse, and the fused launch they do not have — before anything is launched
     if (int rc = planar_refusals(who, in, out, p->flags, have_stages)) return rc;
     if (p->use_rcas && (p->fused == 1 || !have_intermediary))
@@ -884,7 +944,7 @@ static int upscale_decide(const char* who, const fsr1_image* in, bool have_inter
   if (fp_w < 0 || fp_h < 0) return fail(FSR1_ERR_INVALID_ARGUMENT, "%s: scale constants con0.xy = (%g, %g) are not usable", who, sx, sy);
   const bool packed = (plan->math & FSR1_FLAG_MATH_PACKED_FP16) != 0;
   if (!p->use_rcas || p->fused != 1) {  // an EASU dispatch will run (alone, or as the first of two, or as what `auto` may pick)
-    if (easu_lds_bytes(in->format, fp_w, fp_h) > device_lds_per_cu())
+    if (easu_footprint_lds_bytes(in->format, fp_w, fp_h) > device_lds_per_cu())
       return fail(FSR1_ERR_UNSUPPORTED, "%s: input/output ratio (%g, %g) needs a %dx%d texel footprint per tile, beyond the LDS budget", who, sx, sy, fp_w, fp_h);
   }
   if (!p->use_rcas) {
@@ -898,7 +958,7 @@ static int upscale_decide(const char* who, const fsr1_image* in, bool have_inter
   // two dispatches — and where it could only mean the fused launch (no intermediary) the refusal is made here, not by a launch
   if (packed && have_stages && (p->fused == 1 || !have_intermediary))
     return fail(FSR1_ERR_UNSUPPORTED, "%s: the fused launch of packed-fp16 math runs without colour stages; pass an intermediary and fused = 0 or 2", who);
-  const bool fused = p->fused == 1 || (p->fused == 2 && !(packed && have_stages) && !planar && !rgb3 &&
+  const bool fused = p->fused == 1 || (p->fused == 2 && !(packed && have_stages) && !planar && !rgb3 && !mono &&
                                        auto_takes_fused(in, have_intermediary, out, plan->easu_con, plan->math, have_stages));
   if (!fused && !have_intermediary) return fail(FSR1_ERR_INVALID_ARGUMENT, "%s: two-pass EASU+RCAS needs an intermediary image", who);
   if (fused) {  // the fused launch's own LDS bound (fused_dispatch_impl)
@@ -1098,8 +1158,8 @@ int fsr1_pipeline_upscale(fsr1_pipeline* p, const fsr1_image* in, const fsr1_ima
   fsr1_image mid_img;
   const fsr1_image* mid_p = nullptr;
   if (plan.pipeline == 0) {  // two dispatches: this slot's own intermediary, out's extent
-    // (planar: three planes, their rows padded to the RCAS kernel's 16-byte accesses whatever the width; 3-channel: the same padding)
-    const bool padded = is_planar(mid_format) || is_rgb3(mid_format);
+    // (planar: three planes, their rows padded to the RCAS kernel's 16-byte accesses whatever the width; 3-channel, single-channel: the same padding)
+    const bool padded = is_planar(mid_format) || is_rgb3(mid_format) || is_mono(mid_format);
     const size_t row = padded ? ((size_t)out->width * pixel_bytes(mid_format) + 15) & ~(size_t)15 : (size_t)out->width * pixel_bytes(mid_format);
     const size_t need = row * (size_t)image_planes(mid_format) * (size_t)out->height * (size_t)out->frames;
     if (int rc = pipeline_grow(p, slot, need, "pipeline_upscale")) return rc;

@@ -112,7 +112,28 @@ typedef enum fsr1_format {
    * any other format on the other. */
   FSR1_FORMAT_RGB16F = 8,             /* binary16, 6 B/pixel */
   FSR1_FORMAT_RGB32F = 9,             /* binary32, 12 B/pixel */
-  FSR1_FORMAT_RGB8_UNORM = 10         /* 8-bit UNORM, 3 B/pixel */
+  FSR1_FORMAT_RGB8_UNORM = 10,        /* 8-bit UNORM, 3 B/pixel */
+  /* Single-channel (luma / greyscale) images: ONE plane of `height` rows of `width` scalars — the Y plane of a decoded YUV frame, the
+   * (N,1,H,W) tensor of a Y-channel model, greyscale imagery — taken as it is: no replication into RGBA, no slice afterwards.  Rows are
+   * row_pitch_bytes apart (0 = width x element size), frames frame_stride_bytes apart (0 = pitch x height).  Pointer, pitch and frame
+   * stride must be multiples of the ELEMENT size (1, 2 or 4 bytes) and of nothing larger: where they are also multiples of 8 bytes
+   * (uint8: 4) the kernels move two or four columns of a row per access — 4 or 8 bytes, never wider than that alignment — otherwise
+   * element by element.
+   * The output for a luma image L is channel R of FsrEasuF / FsrRcasF evaluated on the image (L, L, L, 1): with R = G = B the reference
+   * performs the same operations on all three channels.  Its luma*2 of such a texel is B*0.5 + (R*0.5 + G) = 0.5 L + round(1.5 L),
+   * which is NOT 2 L for every binary32 L: the kernels evaluate the reference's expression.  R8_UNORM holds 8-bit codes under
+   * RGBA8_UNORM's pinned load / store rules, the uint8 EASU -> RCAS intermediary included.  The contract is the planar formats':
+   * accepted by fsr1_easu_dispatch, fsr1_rcas_dispatch, fsr1_upscale[_ex] / fsr1_upscale_plan / fsr1_pipeline_upscale (and
+   * fsr1_pipeline_reserve) without colour stages (fused = 2 plans the two dispatches), in->format == out->format (and the
+   * intermediary's), default F arithmetic or FSR1_FLAG_MATH_EXACT; FSR1_FLAG_MATH_STRICT takes the EXACT kernels for both passes.
+   * HDR_SQUARE, RCAS_DENOISE, the OUTPUT_* store policies and FRAMES_OVERLAP work as for RGBA; every stored value is channel R of what
+   * the RGBA kernels of the same element type store for the replicated image with alpha 1 (uint8: 255), default arithmetic included.
+   * FSR1_ERR_UNSUPPORTED (the message says "single-channel"): FSR1_FLAG_MATH_PACKED_FP16, colour stages and a single-channel noise
+   * image, fsr1_color_dispatch, row bands, the fused launches (fused = 1, or use_rcas without an intermediary),
+   * FSR1_FLAG_RCAS_PASSTHROUGH_ALPHA, and a single-channel image on one side with any other format on the other. */
+  FSR1_FORMAT_R16F = 11,              /* binary16, 2 B/pixel */
+  FSR1_FORMAT_R32F = 12,              /* binary32, 4 B/pixel */
+  FSR1_FORMAT_R8_UNORM = 13           /* 8-bit UNORM, 1 B/pixel */
 } fsr1_format;
 
 typedef struct fsr1_image {
