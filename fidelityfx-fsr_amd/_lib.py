@@ -54,8 +54,19 @@ class fsr1_color_stages(ctypes.Structure):
     ]
 
 
+class fsr1_ycbcr(ctypes.Structure):
+    """struct fsr1_ycbcr of include/fsr1_hip.h."""
+    _fields_ = [
+        ("m", (ctypes.c_float * 3) * 3),
+        ("bias", ctypes.c_float * 3),
+        ("siting", ctypes.c_int32),
+        ("chroma_offset_bytes", ctypes.c_int64),
+    ]
+
+
 _IMG = ctypes.POINTER(fsr1_image)
 _STG = ctypes.POINTER(fsr1_color_stages)
+_YCC = ctypes.POINTER(fsr1_ycbcr)
 
 # name -> (restype, argtypes); every symbol include/fsr1_hip.h declares
 SYMBOLS = {
@@ -76,6 +87,10 @@ SYMBOLS = {
     "fsr1_upscale": (ctypes.c_int, [ctypes.POINTER(fsr1_image)] * 3 + [ctypes.POINTER(fsr1_params), ctypes.c_void_p]),
     "fsr1_upscale_ex": (ctypes.c_int, [_IMG] * 3 + [ctypes.POINTER(fsr1_params), _STG, ctypes.c_void_p]),
     "fsr1_upscale_plan": (ctypes.c_int, [_IMG, ctypes.c_int32, _IMG, ctypes.POINTER(fsr1_params), ctypes.c_int32]),
+    "fsr1_ycbcr_bt601": (ctypes.c_int, [_YCC, ctypes.c_int]),
+    "fsr1_ycbcr_bt709": (ctypes.c_int, [_YCC, ctypes.c_int]),
+    "fsr1_easu_dispatch_ycbcr": (ctypes.c_int, [_IMG, _IMG, _U32P, _YCC, ctypes.c_uint32, ctypes.c_void_p]),
+    "fsr1_upscale_ycbcr": (ctypes.c_int, [_IMG] * 3 + [ctypes.POINTER(fsr1_params), _YCC, ctypes.c_void_p]),
     "fsr1_pipeline_create": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int32]),
     "fsr1_pipeline_upscale": (ctypes.c_int, [ctypes.c_void_p, _IMG, _IMG, ctypes.POINTER(fsr1_params), _STG]),
     "fsr1_pipeline_reserve": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t]),

@@ -12,7 +12,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import Fsr1Error, fsr1_color_stages, fsr1_image, fsr1_params  # noqa: F401
+from ._lib import Fsr1Error, fsr1_color_stages, fsr1_image, fsr1_params, fsr1_ycbcr  # noqa: F401
 
 FORMAT_RGBA16F = 0
 FORMAT_RGBA32F = 1
@@ -27,6 +27,11 @@ FORMAT_RGB8_UNORM = 10  # the (H,W,3) uint8 frame of a decoder or an OpenCV / PI
 FORMAT_R16F = 11  # one channel (luma / greyscale): a (H,W), (N,H,W) or (N,1,H,W) tensor, marked with Mono()
 FORMAT_R32F = 12
 FORMAT_R8_UNORM = 13  # the Y plane of a decoded frame
+FORMAT_NV12 = 14  # a decoder's surface: 8-bit Y plane + interleaved CbCr plane, marked with Nv12(); input of easu(ycbcr=) / upscale_ycbcr only
+
+CHROMA_REPLICATE = 0  # fsr1_ycbcr.siting (include/fsr1_hip.h)
+CHROMA_LEFT = 1       # H.264 / HEVC default: co-sited horizontally, centred vertically
+CHROMA_CENTER = 2     # JPEG: centred on both axes
 
 FLAG_HDR_SQUARE = 1 << 0
 FLAG_RCAS_DENOISE = 1 << 1
@@ -215,6 +220,80 @@ class Mono:
         return Mono(torch.empty_like(self.t))
 
 
+class Nv12:
+    """Marks a CUDA uint8 tensor shaped (rows, W) or (N, rows, W) as a decoded NV12 surface (FORMAT_NV12) as torch sees it: `height`
+    rows of Y, then — from row rows - ch, ch = (height + 1) // 2 — the rows of interleaved Cb, Cr pairs; rows between the two (a
+    surface whose height is aligned) are skipped.  height defaults to rows * 2 // 3, the tight surface.  Dense along x; the row stride
+    must hold the (W + 1) // 2 chroma pairs, so an odd W needs a padded row.  An input of easu(..., ycbcr=) and upscale_ycbcr only."""
+
+    def __init__(self, t, height=None):
+        self.t, self.height = t, height
+
+    def _surface(self):
+        import torch
+        t = self.t
+        if not t.is_cuda:
+            raise Fsr1Error("image tensors must live on the GPU (got %s); there is no CPU path" % t.device)
+        if t.dtype != torch.uint8:
+            raise Fsr1Error("NV12 surfaces are uint8, got %s" % t.dtype)
+        if t.dim() == 2:
+            t = t.unsqueeze(0)
+        if t.dim() != 3:
+            raise Fsr1Error("expected a (rows, W) or (N, rows, W) NV12 surface, got %s" % (tuple(self.t.shape),))
+        n, rows, w = t.shape
+        h = rows * 2 // 3 if self.height is None else int(self.height)
+        ch = (h + 1) // 2
+        if h < 1 or w < 1 or h + ch > rows:
+            raise Fsr1Error("an NV12 surface of height %d needs %d rows, the tensor has %d" % (h, h + ch, rows))
+        sn, sh, sw = t.stride()
+        if sw != 1:
+            raise Fsr1Error("NV12 surfaces must be dense along x (got a stride of %d elements)" % sw)
+        if sh < (w + 1) // 2 * 2:
+            raise Fsr1Error("row stride %d bytes cannot hold the %d chroma pairs of a %d-pixel row (pad the rows of an odd width)" % (sh, (w + 1) // 2, w))
+        _check_strides(n, rows, w, sn, sh, 1)
+        return fsr1_image(t.data_ptr(), w, h, FORMAT_NV12, n, sh, sn if n > 1 else 0), (rows - ch) * sh
+
+    def image(self):
+        return self._surface()[0]
+
+    def chroma_offset_bytes(self):
+        """Bytes from the first Y byte of a frame to its first Cb byte: what fsr1_ycbcr.chroma_offset_bytes must say for this surface."""
+        return self._surface()[1]
+
+
+class YCbCr:
+    """fsr1_ycbcr: the matrix (raw codes 0..255 in, RGB in {0 to 1} out), bias and chroma siting of the conversion pinned in
+    include/fsr1_hip.h.  YCbCr.bt601(full_range=False) / YCbCr.bt709(...) fill the standard coefficients."""
+
+    def __init__(self, m, bias, siting=CHROMA_LEFT):
+        self.m = np.asarray(m, np.float32).reshape(3, 3)
+        self.bias = np.asarray(bias, np.float32).reshape(3)
+        self.siting = int(siting)
+
+    @classmethod
+    def _standard(cls, fill, full_range, siting):
+        y = fsr1_ycbcr()
+        _lib.check(getattr(_lib.load(), fill)(ctypes.byref(y), int(bool(full_range))))
+        return cls([list(r) for r in y.m], list(y.bias), siting)
+
+    @classmethod
+    def bt601(cls, full_range=False, siting=CHROMA_LEFT):
+        return cls._standard("fsr1_ycbcr_bt601", full_range, siting)
+
+    @classmethod
+    def bt709(cls, full_range=False, siting=CHROMA_LEFT):
+        return cls._standard("fsr1_ycbcr_bt709", full_range, siting)
+
+    def c_struct(self, chroma_offset_bytes=0):
+        y = fsr1_ycbcr()
+        for r in range(3):
+            for c in range(3):
+                y.m[r][c] = float(self.m[r, c])
+            y.bias[r] = float(self.bias[r])
+        y.siting, y.chroma_offset_bytes = self.siting, int(chroma_offset_bytes)
+        return y
+
+
 def image_of(t):
     """fsr1_image descriptor of a CUDA torch tensor:
       float16 / float32 / uint8, shaped (H,W,4) or (N,H,W,4)  -> RGBA16F / RGBA32F / RGBA8_UNORM
@@ -224,7 +303,7 @@ def image_of(t):
       Mono(float16 / float32 / uint8, shaped (H,W), (N,H,W) or (N,1,H,W))  -> R16F / R32F / R8_UNORM
     Row and frame strides are honoured; the innermost (x[, channel]) dims must be dense."""
     import torch
-    if isinstance(t, (Planar, Rgb, Mono)):
+    if isinstance(t, (Planar, Rgb, Mono, Nv12)):  # (Nv12: so that the calls that do not take it refuse it in the library's words)
         return t.image()
     if not t.is_cuda:
         raise Fsr1Error("image tensors must live on the GPU (got %s); there is no CPU path" % t.device)
@@ -310,17 +389,36 @@ def _stages(stages):
     return ctypes.byref(st), (st, keep)
 
 
-def easu(src, dst, con=None, flags=0, stream=None, stages=None):
-    """dst = EASU(src).  con defaults to FsrEasuCon(viewport = input size).  stages: optional ColorStages fused in."""
+def easu(src, dst, con=None, flags=0, stream=None, stages=None, ycbcr=None):
+    """dst = EASU(src).  con defaults to FsrEasuCon(viewport = input size).  stages: optional ColorStages fused in.
+    ycbcr: the YCbCr conversion of an Nv12 source (dst is then a Planar tensor of any of its three dtypes): fsr1_easu_dispatch_ycbcr."""
     i, o = image_of(src), image_of(dst)
     if con is None:
         con = FsrEasuCon(i.width, i.height, i.width, i.height, o.width, o.height)
     con = _con(con, 16)
-    if stages is None:
+    if ycbcr is not None:
+        if stages is not None:
+            raise Fsr1Error("colour stages are not built for NV12 images")
+        y = ycbcr.c_struct(src.chroma_offset_bytes() if isinstance(src, Nv12) else 0)
+        _lib.check(_lib.load().fsr1_easu_dispatch_ycbcr(ctypes.byref(i), ctypes.byref(o), _u32p(con), ctypes.byref(y), flags, _stream_ptr(stream)))
+    elif stages is None:
         _lib.check(_lib.load().fsr1_easu_dispatch(ctypes.byref(i), ctypes.byref(o), _u32p(con), flags, _stream_ptr(stream)))
     else:
         sp, _keep = _stages(stages)
         _lib.check(_lib.load().fsr1_easu_dispatch_ex(ctypes.byref(i), ctypes.byref(o), _u32p(con), flags, sp, _stream_ptr(stream)))
+    return dst
+
+
+def upscale_ycbcr(src, mid, dst, ycbcr, sharpness=0.25, use_rcas=True, fused=0, flags=0, hdr=False, stream=None, render_size=None):
+    """dst = Upscale(src) for an Nv12 source (fsr1_upscale_ycbcr): the NV12 EASU into `mid` — a Planar tensor of dst's dtype and shape,
+    None when use_rcas is False — then the planar RCAS; EASU only without RCAS.  fused: 0 or 2 (two dispatches); 1 is refused."""
+    i, o = image_of(src), image_of(dst)
+    m = image_of(mid) if mid is not None else None
+    rw, rh = render_size if render_size is not None else (i.width, i.height)
+    p = fsr1_params(float(rw), float(rh), int(bool(use_rcas)), float(sharpness), int(bool(hdr)), int(fused) if use_rcas else 0, int(flags))
+    y = ycbcr.c_struct(src.chroma_offset_bytes() if isinstance(src, Nv12) else 0)
+    _lib.check(_lib.load().fsr1_upscale_ycbcr(ctypes.byref(i), ctypes.byref(m) if m is not None else None, ctypes.byref(o), ctypes.byref(p),
+                                              ctypes.byref(y), _stream_ptr(stream)))
     return dst
 
 

@@ -54,6 +54,8 @@ size_t easu_mono_lds_bytes(int fp_w, int fp_h);
 hipError_t rcas_mono_launch(const RcasArgs& a, int fmt, bool exact, bool wide, hipStream_t stream);
 void rcas_mono_geometry(int fmt, int width, int height, int frames, bool overlapped, int cus, int* tiles_x, int* tiles_y, int* rows);
 size_t rcas_mono_access_bytes(int fmt);
+hipError_t easu_nv12_launch(const EasuArgs& a, const fsr1_ycbcr& ycbcr, long long chroma_offset, int fout, bool exact, bool s2, bool wide, hipStream_t stream);
+size_t easu_nv12_lds_bytes(int fp_w, int fp_h);
 }  // namespace fsr1
 
 using namespace fsr1;
@@ -163,6 +165,13 @@ static size_t pixel_bytes(int fmt) {
   return fmt == FSR1_FORMAT_RGBA32F ? 16 : (fmt == FSR1_FORMAT_RGBA16F ? 8 : 4);
 }
 
+// NV12 (fsr1_hip.h) is an input of fsr1_easu_dispatch_ycbcr / fsr1_upscale_ycbcr alone: what every other entry point answers
+static int nv12_refusal(const char* name) {
+  return fail(FSR1_ERR_UNSUPPORTED, "%s: NV12 images are an input of fsr1_easu_dispatch_ycbcr / fsr1_upscale_ycbcr only", name);
+}
+
+static bool any_nv12(const fsr1_image* a, const fsr1_image* b) { return (a && a->format == FSR1_FORMAT_NV12) || (b && b->format == FSR1_FORMAT_NV12); }
+
 static int check_image(const fsr1_image* im, const char* name, ImageView* v) {
   if (!im) return fail(FSR1_ERR_INVALID_ARGUMENT, "%s: null image descriptor", name);
   if (!im->data) return fail(FSR1_ERR_INVALID_ARGUMENT, "%s: null data pointer", name);
@@ -170,6 +179,7 @@ static int check_image(const fsr1_image* im, const char* name, ImageView* v) {
     return fail(FSR1_ERR_INVALID_ARGUMENT, "%s: bad extent %dx%dx%d", name, im->width, im->height, im->frames);
   if (im->width > (1 << 20) || im->height > (1 << 20))  // pixel coordinates stay exact in binary32 with room to spare
     return fail(FSR1_ERR_UNSUPPORTED, "%s: extent %dx%d beyond 2^20 pixels per side", name, im->width, im->height);
+  if (im->format == FSR1_FORMAT_NV12) return nv12_refusal(name);
   if (!format_known(im->format))
     return fail(FSR1_ERR_UNSUPPORTED, "%s: unsupported format %d", name, im->format);
   const size_t px = pixel_bytes(im->format);
@@ -415,6 +425,7 @@ int fsr1_easu_dispatch_band(const fsr1_image* in, const fsr1_image* out, const u
   if (origin_x < 0 || origin_y < 0 || origin_x > (1 << 20) || origin_y > (1 << 20))
     return fail(FSR1_ERR_INVALID_ARGUMENT, "easu band: origin (%d, %d) out of range", origin_x, origin_y);
   if (flags & FSR1_FLAG_MATH_PACKED_FP16) return fail(FSR1_ERR_UNSUPPORTED, "easu band: bands run with the F (binary32) arithmetic");
+  if (any_nv12(in, out)) return nv12_refusal("easu band");
   if (any_mono(in, out)) return fail(FSR1_ERR_UNSUPPORTED, "easu band: row bands are not built for single-channel images");
   if (any_rgb3(in, out)) return fail(FSR1_ERR_UNSUPPORTED, "easu band: row bands are not built for 3-channel images");
   if (any_planar(in, out)) return fail(FSR1_ERR_UNSUPPORTED, "easu band: row bands are not built for planar images");
@@ -454,17 +465,11 @@ static int mono_refusals(const char* who, const fsr1_image* in, const fsr1_image
 // The 3-channel kernels take the four-element access (4 / 8 / 16 bytes) only where every address they form with it is aligned to it.
 static bool rgb3_wide(const fsr1_image* im, const ImageView& v) { return planar_aligned(im, v, 4 * rgb3_element_bytes(im->format)); }
 
-// EASU on planar and on 3-channel images: `a` holds the checked views.  The interleaved dispatch's tile geometry without its tall-tile,
-// F-strict and pitched-LDS variants; FSR1_FLAG_MATH_STRICT takes the EXACT kernel (which is what it promises: EXACT's stored image).
-// Single-channel images take the same road with their own kernel and its smaller LDS footprint.
-static int easu_planar_dispatch(const fsr1_image* in, const fsr1_image* out, EasuArgs& a, const uint32_t con[16], uint32_t flags, void* stream) {
-  const bool mono = any_mono(in, out), rgb3 = !mono && any_rgb3(in, out);
-  if (int rc = mono ? mono_refusals("easu", in, out, flags, a.color.stages != 0)
-               : rgb3 ? rgb3_refusals("easu", in, out, flags, a.color.stages != 0) : planar_refusals("easu", in, out, flags, a.color.stages != 0)) return rc;
-  if (!con) return fail(FSR1_ERR_INVALID_ARGUMENT, "easu: null constants");
-  if (in->frames != out->frames) return fail(FSR1_ERR_INVALID_ARGUMENT, "easu: frame counts differ (%d vs %d)", in->frames, out->frames);
-  if (overlaps(in, a.in, out, a.out)) return fail(FSR1_ERR_INVALID_ARGUMENT, "easu: input and output overlap");
-  const bool exact = (flags & (FSR1_FLAG_MATH_EXACT | FSR1_FLAG_MATH_STRICT)) != 0;
+// The part of an EASU dispatch on planar-like images that the constants and the OUTPUT decide, shared with the NV12 dispatch: footprint,
+// LDS bound, tiles, store policy and whether the exact-2x variant applies.  The interleaved dispatch's tile geometry without its
+// tall-tile, F-strict and pitched-LDS variants.  `a` holds the checked views; lds_bytes(lds_fmt, fp_w, fp_h): the kernel's LDS need.
+static int easu_planar_geometry(const fsr1_image* out, EasuArgs& a, const uint32_t con[16], uint32_t flags, size_t (*lds_bytes)(int, int, int), int lds_fmt,
+                                bool* s2_out) {
   memcpy(a.con, con, sizeof a.con);
   float sx, sy, bx, by;
   memcpy(&sx, &con[0], 4);
@@ -475,7 +480,7 @@ static int easu_planar_dispatch(const fsr1_image* in, const fsr1_image* out, Eas
   a.fp_w = footprint_extent(out->width, kTileW, 0, sx, bx);
   a.fp_h = footprint_extent(out->height, kTileH, 0, sy, by);
   if (a.fp_w < 0 || a.fp_h < 0) return fail(FSR1_ERR_INVALID_ARGUMENT, "easu: scale constants con0.xy = (%g, %g) are not usable", sx, sy);
-  if (easu_footprint_lds_bytes(in->format, a.fp_w, a.fp_h) > device_lds_per_cu())
+  if (lds_bytes(lds_fmt, a.fp_w, a.fp_h) > device_lds_per_cu())
     return fail(FSR1_ERR_UNSUPPORTED, "easu: input/output ratio (%g, %g) needs a %dx%d texel footprint per tile, beyond the LDS budget "
                                       "(EASU is an upscaler; ratios up to ~3x minification are supported)", sx, sy, a.fp_w, a.fp_h);
   if ((long long)(a.fp_h + 1) * a.in.pitch >= (1ll << 31))
@@ -492,7 +497,22 @@ static int easu_planar_dispatch(const fsr1_image* in, const fsr1_image* out, Eas
     a.fp_w = kTileW / 2 + 3;
     a.fp_h = kTileH / 2 + 3;
   }
-  if (int rc = check_grid("easu", a.tiles_x, a.tiles_y, a.frames)) return rc;
+  *s2_out = s2;
+  return check_grid("easu", a.tiles_x, a.tiles_y, a.frames);
+}
+
+// EASU on planar and on 3-channel images: `a` holds the checked views.  FSR1_FLAG_MATH_STRICT takes the EXACT kernel (which is what it
+// promises: EXACT's stored image).  Single-channel images take the same road with their own kernel and its smaller LDS footprint.
+static int easu_planar_dispatch(const fsr1_image* in, const fsr1_image* out, EasuArgs& a, const uint32_t con[16], uint32_t flags, void* stream) {
+  const bool mono = any_mono(in, out), rgb3 = !mono && any_rgb3(in, out);
+  if (int rc = mono ? mono_refusals("easu", in, out, flags, a.color.stages != 0)
+               : rgb3 ? rgb3_refusals("easu", in, out, flags, a.color.stages != 0) : planar_refusals("easu", in, out, flags, a.color.stages != 0)) return rc;
+  if (!con) return fail(FSR1_ERR_INVALID_ARGUMENT, "easu: null constants");
+  if (in->frames != out->frames) return fail(FSR1_ERR_INVALID_ARGUMENT, "easu: frame counts differ (%d vs %d)", in->frames, out->frames);
+  if (overlaps(in, a.in, out, a.out)) return fail(FSR1_ERR_INVALID_ARGUMENT, "easu: input and output overlap");
+  const bool exact = (flags & (FSR1_FLAG_MATH_EXACT | FSR1_FLAG_MATH_STRICT)) != 0;
+  bool s2 = false;
+  if (int rc = easu_planar_geometry(out, a, con, flags, easu_footprint_lds_bytes, in->format, &s2)) return rc;
   // the exact-2x variant's pair stores; 8-bit planes: its dword stores
   // (3-channel: its flat run of four-element stores; single-channel: pairs and dwords like planar's)
   const bool u8 = out->format == FSR1_FORMAT_RGB8_UNORM_PLANAR || out->format == FSR1_FORMAT_R8_UNORM;
@@ -620,6 +640,7 @@ int fsr1_rcas_dispatch_band(const fsr1_image* in, const fsr1_image* out, const u
                             int32_t rows_below, void* stream) {
   if ((rows_above | rows_below) & ~1) return fail(FSR1_ERR_INVALID_ARGUMENT, "rcas band: rows_above / rows_below must be 0 or 1");
   if (flags & FSR1_FLAG_MATH_PACKED_FP16) return fail(FSR1_ERR_UNSUPPORTED, "rcas band: bands run with the F (binary32) arithmetic");
+  if (any_nv12(in, out)) return nv12_refusal("rcas band");
   if (any_mono(in, out)) return fail(FSR1_ERR_UNSUPPORTED, "rcas band: row bands are not built for single-channel images");
   if (any_rgb3(in, out)) return fail(FSR1_ERR_UNSUPPORTED, "rcas band: row bands are not built for 3-channel images");
   if (any_planar(in, out)) return fail(FSR1_ERR_UNSUPPORTED, "rcas band: row bands are not built for planar images");
@@ -890,6 +911,7 @@ static int upscale_decide(const char* who, const fsr1_image* in, bool have_inter
   for (const fsr1_image* im : {in, out}) {
     if (im->width <= 0 || im->height <= 0 || im->frames <= 0)
       return fail(FSR1_ERR_INVALID_ARGUMENT, "%s: bad %s extent %dx%dx%d", who, im == in ? "input" : "output", im->width, im->height, im->frames);
+    if (im->format == FSR1_FORMAT_NV12) return nv12_refusal(who);
     if (!format_known(im->format))
       return fail(FSR1_ERR_UNSUPPORTED, "%s: unsupported %s format %d", who, im == in ? "input" : "output", im->format);
   }
@@ -1008,6 +1030,108 @@ int fsr1_upscale_plan(const fsr1_image* in, int32_t have_intermediary, const fsr
   UpscalePlan plan;
   if (int rc = upscale_decide("upscale_plan", in, have_intermediary != 0, out, p, have_stages != 0, &plan)) return rc;
   return plan.pipeline;
+}
+
+// ---- NV12 in, planar RGB out (include/fsr1_hip.h, fsr1_easu_nv12.hip) ----
+// An NV12 descriptor and its fsr1_ycbcr -> the view of the Y plane (whose pitch and frame stride the chroma plane shares), the resolved
+// chroma offset and the bytes of one frame.  check_image's rules with the element being a Cb, Cr pair: multiples of 2 everywhere.
+static int check_nv12(const fsr1_image* im, const fsr1_ycbcr* yc, const char* name, ImageView* v, long long* chroma_offset, long long* frame_bytes) {
+  if (!im) return fail(FSR1_ERR_INVALID_ARGUMENT, "%s: null image descriptor", name);
+  if (im->format != FSR1_FORMAT_NV12) return fail(FSR1_ERR_UNSUPPORTED, "%s: the input must be FSR1_FORMAT_NV12, got format %d", name, im->format);
+  if (!yc) return fail(FSR1_ERR_INVALID_ARGUMENT, "%s: null fsr1_ycbcr", name);
+  if (!im->data) return fail(FSR1_ERR_INVALID_ARGUMENT, "%s: null data pointer", name);
+  if (im->width <= 0 || im->height <= 0 || im->frames <= 0)
+    return fail(FSR1_ERR_INVALID_ARGUMENT, "%s: bad extent %dx%dx%d", name, im->width, im->height, im->frames);
+  if (im->width > (1 << 20) || im->height > (1 << 20))
+    return fail(FSR1_ERR_UNSUPPORTED, "%s: extent %dx%d beyond 2^20 pixels per side", name, im->width, im->height);
+  if (yc->siting != FSR1_CHROMA_REPLICATE && yc->siting != FSR1_CHROMA_LEFT && yc->siting != FSR1_CHROMA_CENTER)
+    return fail(FSR1_ERR_UNSUPPORTED, "%s: unknown NV12 chroma siting %d", name, yc->siting);
+  const long long cw = (im->width + 1) / 2, ch = (im->height + 1) / 2;
+  const long long pitch = im->row_pitch_bytes ? im->row_pitch_bytes : 2 * cw;
+  if (pitch < 2 * cw || pitch % 2)
+    return fail(FSR1_ERR_INVALID_ARGUMENT, "%s: NV12 row pitch %lld must be even and hold %lld bytes of chroma pairs", name, pitch, 2 * cw);
+  const long long coff = yc->chroma_offset_bytes ? yc->chroma_offset_bytes : pitch * im->height;
+  if (coff < pitch * im->height || coff % 2 || coff > (1ll << 40))
+    return fail(FSR1_ERR_INVALID_ARGUMENT, "%s: NV12 chroma offset %lld must be even and at least pitch x height = %lld", name, coff, pitch * im->height);
+  const long long fbytes = coff + pitch * ch;
+  const long long fstride = im->frame_stride_bytes ? im->frame_stride_bytes : fbytes;
+  if (im->frames > 1 && fstride < fbytes) return fail(FSR1_ERR_INVALID_ARGUMENT, "%s: frame stride %lld smaller than one NV12 frame", name, fstride);
+  if (((uintptr_t)im->data % 2) || (fstride % 2)) return fail(FSR1_ERR_INVALID_ARGUMENT, "%s: NV12 data pointer / frame stride must be even", name);
+  v->base = static_cast<char*>(im->data);
+  v->width = im->width;
+  v->height = im->height;
+  v->pitch = pitch;
+  v->frame_stride = fstride;
+  *chroma_offset = coff;
+  *frame_bytes = fbytes;
+  return FSR1_OK;
+}
+
+static size_t nv12_footprint_lds_bytes(int, int fp_w, int fp_h) { return easu_nv12_lds_bytes(fp_w, fp_h); }  // records + the chroma pairs
+
+int fsr1_easu_dispatch_ycbcr(const fsr1_image* in, const fsr1_image* out, const uint32_t con[16], const fsr1_ycbcr* ycbcr, uint32_t flags,
+                             void* stream) {
+  const Range range("easu_ycbcr", in, out);
+  EasuArgs a;
+  a.xcd_shift = device_xcd_shift();
+  memset(&a.color, 0, sizeof a.color);
+  long long chroma_offset = 0, frame_bytes = 0;
+  if (int rc = check_flags(flags)) return rc;
+  if (int rc = check_nv12(in, ycbcr, "easu_ycbcr input", &a.in, &chroma_offset, &frame_bytes)) return rc;
+  if (out && out->format == FSR1_FORMAT_NV12) return fail(FSR1_ERR_UNSUPPORTED, "easu_ycbcr output: NV12 as an output is not built");
+  if (int rc = check_image(out, "easu_ycbcr output", &a.out)) return rc;
+  if (!is_planar(out->format))
+    return fail(FSR1_ERR_UNSUPPORTED, "easu_ycbcr: an NV12 input needs a planar output (RGB16F_PLANAR, RGB32F_PLANAR or RGB8_UNORM_PLANAR), got format %d", out->format);
+  if (flags & FSR1_FLAG_MATH_PACKED_FP16) return fail(FSR1_ERR_UNSUPPORTED, "easu_ycbcr: NV12 images run with the F (binary32) arithmetic, not packed fp16");
+  if (!con) return fail(FSR1_ERR_INVALID_ARGUMENT, "easu_ycbcr: null constants");
+  if (in->frames != out->frames) return fail(FSR1_ERR_INVALID_ARGUMENT, "easu_ycbcr: frame counts differ (%d vs %d)", in->frames, out->frames);
+  {  // the overlap test of the other dispatches, over what an NV12 batch occupies: its last frame ends behind its chroma plane
+    const char* const i0 = a.in.base;
+    const char* const i1 = a.in.base + a.in.frame_stride * (in->frames - 1) + frame_bytes;
+    const char* const o0 = a.out.base;
+    const char* const o1 = a.out.base + a.out.frame_stride * (out->frames - 1) + a.out.pitch * out->height * image_planes(out->format);
+    if (i0 < o1 && o0 < i1) return fail(FSR1_ERR_INVALID_ARGUMENT, "easu_ycbcr: input and output overlap");
+  }
+  const bool exact = (flags & (FSR1_FLAG_MATH_EXACT | FSR1_FLAG_MATH_STRICT)) != 0;
+  bool s2 = false;
+  if (int rc = easu_planar_geometry(out, a, con, flags, nv12_footprint_lds_bytes, in->format, &s2)) return rc;
+  const bool wide = planar_aligned(out, a.out, out->format == FSR1_FORMAT_RGB8_UNORM_PLANAR ? 4 : 2 * pixel_bytes(out->format));
+  if (const hipError_t e = easu_nv12_launch(a, *ycbcr, chroma_offset, out->format, exact, s2, wide, static_cast<hipStream_t>(stream)); e != hipSuccess)
+    return hip_fail(e, "easu_ycbcr launch");
+  return FSR1_OK;
+}
+
+// FSR_Filter::Upscale for a decoder's frame: fsr1_upscale_ex's two-dispatch road with the NV12 EASU in front.
+int fsr1_upscale_ycbcr(const fsr1_image* in, const fsr1_image* intermediary, const fsr1_image* out, const fsr1_params* p,
+                       const fsr1_ycbcr* ycbcr, void* stream) {
+  const Range range("upscale_ycbcr", in, out);
+  if (!in || !out || !p) return fail(FSR1_ERR_INVALID_ARGUMENT, "upscale_ycbcr: null argument");
+  if (in->format != FSR1_FORMAT_NV12) return fail(FSR1_ERR_UNSUPPORTED, "upscale_ycbcr: the input must be FSR1_FORMAT_NV12, got format %d", in->format);
+  if (!is_planar(out->format) || (p->use_rcas && intermediary && intermediary->format != out->format))  // (before anything is launched)
+    return fail(FSR1_ERR_UNSUPPORTED, "upscale_ycbcr: an NV12 input needs a planar output and an intermediary of the same planar format");
+  if (int rc = check_flags(p->flags)) return rc;
+  const uint32_t math = p->flags & (FSR1_FLAG_MATH_EXACT | FSR1_FLAG_MATH_PACKED_FP16 | FSR1_FLAG_MATH_STRICT | FSR1_FLAG_NO_FAST_PATHS | FSR1_FLAG_FRAMES_OVERLAP);
+  const uint32_t rcas_opts = p->flags & FSR1_FLAG_RCAS_DENOISE;
+  const uint32_t out_policy = p->flags & (FSR1_FLAG_OUTPUT_STREAMING | FSR1_FLAG_OUTPUT_CACHED);  // of the pass that writes `out`
+  if (p->flags & ~(math | rcas_opts | out_policy))
+    return fail(FSR1_ERR_INVALID_ARGUMENT, "upscale_ycbcr: params.flags may only hold MATH_*, RCAS_DENOISE, OUTPUT_* and FRAMES_OVERLAP bits");
+  if (p->use_rcas && p->fused != 0 && p->fused != 1 && p->fused != 2) return fail(FSR1_ERR_INVALID_ARGUMENT, "upscale_ycbcr: params.fused must be 0, 1 or 2 (auto)");
+  if (p->use_rcas && (p->fused == 1 || !intermediary))
+    return fail(FSR1_ERR_UNSUPPORTED, "upscale_ycbcr: NV12 images run as two dispatches; pass an intermediary and fused = 0 or 2");
+  if (in->width <= 0 || in->height <= 0 || out->width <= 0 || out->height <= 0)
+    return fail(FSR1_ERR_INVALID_ARGUMENT, "upscale_ycbcr: bad extent %dx%d -> %dx%d", in->width, in->height, out->width, out->height);
+  if (!(p->render_width >= 1.0f) || !(p->render_height >= 1.0f) || p->render_width > (float)in->width || p->render_height > (float)in->height)
+    return fail(FSR1_ERR_INVALID_ARGUMENT, "upscale_ycbcr: render size %gx%g must lie within the input image %dx%d", (double)p->render_width,
+                (double)p->render_height, in->width, in->height);
+  uint32_t easu_con[16], rcas_con[4];
+  FsrEasuCon(easu_con, easu_con + 4, easu_con + 8, easu_con + 12, p->render_width, p->render_height, p->render_width, p->render_height,
+             (float)out->width, (float)out->height);  // FSR_Filter.cpp:106
+  if (!p->use_rcas)  // :107 Sample.x = hdr && !bUseRcas ; :140 EASU straight into the output
+    return fsr1_easu_dispatch_ycbcr(in, out, easu_con, ycbcr,
+                                    math | (p->hdr ? FSR1_FLAG_HDR_SQUARE : 0u) | (out_policy ? out_policy : (uint32_t)FSR1_FLAG_OUTPUT_STREAMING), stream);
+  if (int rc = fsr1_easu_dispatch_ycbcr(in, intermediary, easu_con, ycbcr, math, stream)) return rc;  // :121
+  FsrRcasCon(rcas_con, p->rcas_attenuation);                                                          // :124
+  return fsr1_rcas_dispatch(intermediary, out, rcas_con, math | rcas_opts | out_policy | (p->hdr ? FSR1_FLAG_HDR_SQUARE : 0u), stream);  // :131
 }
 
 int fsr1_selftest(uint32_t* failures) {

@@ -83,3 +83,27 @@ void FsrRcasCon(uint32_t* con, float sharpness) {
   con[2] = 0;
   con[3] = 0;
 }
+
+/* YCbCr -> RGB matrices for raw 8-bit codes in, RGB in {0 to 1} out (fsr1_ycbcr, include/fsr1_hip.h).  With the luma weights
+ * Kr, Kb (Kg = 1 - Kr - Kb) of the standard and E'y = (Y - y0) / ys, E'pb = (Cb - 128) / cs, E'pr = (Cr - 128) / cs:
+ *   R = E'y + 2 (1 - Kr) E'pr,  G = E'y - 2 Kb (1 - Kb) / Kg E'pb - 2 Kr (1 - Kr) / Kg E'pr,  B = E'y + 2 (1 - Kb) E'pb
+ * (y0, ys, cs) = (16, 219, 224) for limited ("video") range, (0, 255, 255) for full range.  Every coefficient is formed in double and
+ * rounded to float once. */
+static int ycbcr_fill(fsr1_ycbcr* y, double kr, double kb, int full_range) {
+  if (!y) return FSR1_ERR_INVALID_ARGUMENT;
+  const double kg = 1.0 - kr - kb;
+  const double y0 = full_range ? 0.0 : 16.0, ys = full_range ? 255.0 : 219.0, cs = full_range ? 255.0 : 224.0;
+  const double m[3][3] = {{1.0 / ys, 0.0, 2.0 * (1.0 - kr) / cs},
+                          {1.0 / ys, -2.0 * kb * (1.0 - kb) / kg / cs, -2.0 * kr * (1.0 - kr) / kg / cs},
+                          {1.0 / ys, 2.0 * (1.0 - kb) / cs, 0.0}};
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c) y->m[r][c] = (float)m[r][c];
+    y->bias[r] = (float)(-(y0 * m[r][0] + 128.0 * (m[r][1] + m[r][2])));
+  }
+  y->siting = FSR1_CHROMA_LEFT;
+  y->chroma_offset_bytes = 0;
+  return FSR1_OK;
+}
+
+int fsr1_ycbcr_bt601(fsr1_ycbcr* ycbcr, int full_range) { return ycbcr_fill(ycbcr, 0.299, 0.114, full_range); }
+int fsr1_ycbcr_bt709(fsr1_ycbcr* ycbcr, int full_range) { return ycbcr_fill(ycbcr, 0.2126, 0.0722, full_range); }

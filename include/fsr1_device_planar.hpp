@@ -56,6 +56,23 @@ template <> struct Plane<FSR1_FORMAT_RGB8_UNORM_PLANAR> {
 // bytes between the planes of a frame
 __device__ __forceinline__ long long plane_stride(const ImageView& v) { return v.pitch * (long long)v.height; }
 
+// Phase 2 of easu_stage_footprint on the dense LDS layout, behind the barrier that ends a phase 1: FsrEasuSetF's terms for columns
+// 1 .. fw - 2, rows 1 .. fh - 2 of the footprint.  Shared by the stagings that differ in phase 1 only (planes here, NV12 in
+// fsr1_device_nv12.hpp).  FW: compile-time footprint width, 0 = run-time.  Ends with a barrier.
+template <bool EXACT, int FW, int THREADS>
+__device__ __forceinline__ void easu_stage_analysis(const EasuLds& l, int fw, int fh, int tid) {
+  __syncthreads();
+  const int iw = fw - 2, m = iw * (fh - 2);
+  const float inv_iw = __builtin_amdgcn_rcpf((float)iw);
+  const float* const lum = reinterpret_cast<const float*>(l.tex) + 3;
+  for (int j = tid; j < m; j += THREADS) {
+    const int y = FW ? j / (FW - 2) : (int)(((float)j + 0.5f) * inv_iw);
+    const int i = (y + 1) * fw + (j - y * iw) + 1;
+    l.ana[i] = easu_analysis<EXACT>(lum[4 * (i - fw)], lum[4 * (i - 1)], lum[4 * i], lum[4 * (i + 1)], lum[4 * (i + fw)]);
+  }
+  __syncthreads();
+}
+
 // Phases 1 and 2 of easu_stage_footprint for a planar input: the same LDS records (R, G, B, luma*2 | analysis) for the footprint
 // [fx0, fx0 + fw) x [fy0, fy0 + fh) with the sampler's clamp-to-edge applied, so phase 3 runs unchanged.  One wave per footprint
 // row, one lane per footprint column: the three plane-row bases are scalar, a lane reads its (clamped) column from each plane,
@@ -112,17 +129,7 @@ __device__ __forceinline__ void easu_stage_footprint_planar(const EasuLds& l, co
       l.tex[i] = record(*reinterpret_cast<const elem_t*>(p), *reinterpret_cast<const elem_t*>(p + ps), *reinterpret_cast<const elem_t*>(p + 2 * ps));
     }
   }
-  __syncthreads();
-  // phase 2, as in easu_stage_footprint: FsrEasuSetF's terms for columns 1 .. fw - 2, rows 1 .. fh - 2 of the footprint
-  const int iw = fw - 2, m = iw * (fh - 2);
-  const float inv_iw = __builtin_amdgcn_rcpf((float)iw);
-  const float* const lum = reinterpret_cast<const float*>(l.tex) + 3;
-  for (int j = tid; j < m; j += THREADS) {
-    const int y = FW ? j / (FW - 2) : (int)(((float)j + 0.5f) * inv_iw);
-    const int i = (y + 1) * fw + (j - y * iw) + 1;
-    l.ana[i] = easu_analysis<EXACT>(lum[4 * (i - fw)], lum[4 * (i - 1)], lum[4 * i], lum[4 * (i + 1)], lum[4 * (i + fw)]);
-  }
-  __syncthreads();
+  easu_stage_analysis<EXACT, FW, THREADS>(l, fw, fh, tid);
 }
 
 // One value per plane at column / row address `o` of plane R (`ps` bytes between planes).

@@ -133,7 +133,21 @@ typedef enum fsr1_format {
    * FSR1_FLAG_RCAS_PASSTHROUGH_ALPHA, and a single-channel image on one side with any other format on the other. */
   FSR1_FORMAT_R16F = 11,              /* binary16, 2 B/pixel */
   FSR1_FORMAT_R32F = 12,              /* binary32, 4 B/pixel */
-  FSR1_FORMAT_R8_UNORM = 13           /* 8-bit UNORM, 1 B/pixel */
+  FSR1_FORMAT_R8_UNORM = 13,          /* 8-bit UNORM, 1 B/pixel */
+  /* NV12 — 4:2:0 YCbCr as a hardware decoder writes it — INPUT ONLY, and only of fsr1_easu_dispatch_ycbcr / fsr1_upscale_ycbcr
+   * (below, with the pinned conversion); every other entry point, and NV12 as an output, is FSR1_ERR_UNSUPPORTED with "NV12" in the
+   * message.  A frame is a full-resolution plane of 8-bit Y codes followed by a plane of interleaved (Cb, Cr) byte pairs at half the
+   * resolution each way.  fsr1_image describes it unchanged:
+   *   width / height      the LUMA size, any size >= 1, odd included; the chroma plane is cw = (width + 1) / 2 pairs by
+   *                       ch = (height + 1) / 2 rows
+   *   row_pitch_bytes     shared by both planes; 0 = 2 * cw (= width rounded up to even); it must hold 2 * cw bytes (and with them
+   *                       the `width` bytes of a Y row)
+   *   the chroma plane    starts fsr1_ycbcr.chroma_offset_bytes after `data` (0 = pitch * height: directly behind the last Y row;
+   *                       otherwise >= that — a surface whose height is aligned keeps it at pitch * aligned height)
+   *   frame_stride_bytes  0 = chroma offset + pitch * ch
+   * Pointer, pitch, chroma offset and frame stride need only be multiples of 2: the kernel reads Y bytes and 16-bit pairs, nothing
+   * wider, whatever the alignment. */
+  FSR1_FORMAT_NV12 = 14               /* 8-bit Y plane + interleaved CbCr plane, 1.5 B/pixel */
 } fsr1_format;
 
 typedef struct fsr1_image {
@@ -384,6 +398,58 @@ int fsr1_upscale_ex(const fsr1_image* in, const fsr1_image* intermediary, const 
  * uses fused = 2 ("auto") account bytes and report timings for the path actually taken (runner/fsr1_runner.c). */
 int fsr1_upscale_plan(const fsr1_image* in, int32_t have_intermediary, const fsr1_image* out, const fsr1_params* params,
                       int32_t have_stages);
+
+/* ------------------------------------------------------------------------------------------------
+ * NV12 in, planar RGB out: the colour conversion happens inside EASU's footprint staging, once per input texel — no conversion
+ * pass, no RGB copy of the frame.
+ *
+ * THE PINNED CONVERSION (the parity contract, like the UNORM rules above).  The RGB image EASU filters is defined PER LUMA TEXEL
+ * (x, y), 0 <= x < width, 0 <= y < height; EASU's clamp-to-edge acts on luma coordinates first, the chroma indices below are then
+ * clamped to the chroma plane [0, cw - 1] x [0, ch - 1].  Y, Cb, Cr are the raw codes 0 .. 255 as binary32.
+ *   Chroma reconstruction, for C = Cb and C = Cr alike.  k = x >> 1, o = x & 1 horizontally, j = y >> 1, o = y & 1 vertically:
+ *     co-sited   o ? 0.5 * C[k] + 0.5 * C[k + 1] : C[k]
+ *     centred    0.75 * C[k] + 0.25 * C[k + (o ? 1 : -1)]
+ *     FSR1_CHROMA_REPLICATE  C[k], C[j]: the pair of the texel's 2 x 2 block on both axes
+ *     FSR1_CHROMA_LEFT       co-sited horizontally, centred vertically (the H.264 / HEVC / MPEG-2 default)
+ *     FSR1_CHROMA_CENTER     centred on both axes (JPEG / MPEG-1)
+ *   horizontally first (on chroma rows j and j +- 1), then vertically, in binary32.  Every product and sum here is exact (8-bit
+ *   codes, weights in sixteenths), so the order of these operations cannot matter.
+ *   Conversion, per channel c of R, G, B — each multiplication and each addition rounded to binary32 BY ITSELF, round-to-nearest-even,
+ *   never contracted into a fused multiply-add, in every arithmetic mode:
+ *     v = bias[c] + m[c][0] * Y
+ *     v = v + m[c][1] * Cb
+ *     v = v + m[c][2] * Cr
+ *     result = min(max(v, 0), 1)
+ * A binary32 restatement of these lines (numpy float32) reproduces the staged RGB bit for bit, and the image EASU then stores is the one
+ * the planar kernels store for that RGB image in out's format — bit for bit, default arithmetic included.
+ * ---------------------------------------------------------------------------------------------- */
+enum { FSR1_CHROMA_REPLICATE = 0, FSR1_CHROMA_LEFT = 1, FSR1_CHROMA_CENTER = 2 };
+
+typedef struct fsr1_ycbcr {
+  float m[3][3];               /* rows R, G, B; columns Y, Cb, Cr: raw codes 0 .. 255 in, RGB in {0 to 1} out */
+  float bias[3];
+  int32_t siting;              /* FSR1_CHROMA_* */
+  int64_t chroma_offset_bytes; /* 0 = pitch * height; otherwise the byte offset of the CbCr plane from `data` (aligned surface heights) */
+} fsr1_ycbcr;
+
+/* Fill m and bias for ITU-R BT.601 / BT.709, limited ("video": Y 16 .. 235, C 16 .. 240) or full range; the coefficients are computed in
+ * double and rounded once to float.  siting = FSR1_CHROMA_LEFT, chroma_offset_bytes = 0.  Host, pure. */
+int fsr1_ycbcr_bt601(fsr1_ycbcr* ycbcr, int full_range);
+int fsr1_ycbcr_bt709(fsr1_ycbcr* ycbcr, int full_range);
+
+/* EASU of an NV12 image into a planar RGB image (FSR1_FORMAT_RGB16F_PLANAR / RGB32F_PLANAR / RGB8_UNORM_PLANAR: the caller picks the
+ * output type, the input has none to match).  fsr1_easu_dispatch's validation and overlap test (the chroma plane at its offset
+ * included); default F arithmetic or FSR1_FLAG_MATH_EXACT, FSR1_FLAG_MATH_STRICT takes EXACT as for planar; HDR_SQUARE, OUTPUT_* and
+ * FRAMES_OVERLAP as for planar.  FSR1_ERR_UNSUPPORTED ("NV12" in the message): an input that is not NV12, an output that is not one
+ * of the three planar formats (NV12 included), FSR1_FLAG_MATH_PACKED_FP16, an unknown siting. */
+int fsr1_easu_dispatch_ycbcr(const fsr1_image* in, const fsr1_image* out, const uint32_t con[16], const fsr1_ycbcr* ycbcr, uint32_t flags,
+                             void* stream);
+
+/* fsr1_upscale for an NV12 input: the EASU above into a planar intermediary of out's format, then the planar RCAS dispatch;
+ * use_rcas == 0 is EASU only (the intermediary may be NULL).  fused = 1, or use_rcas without an intermediary, is FSR1_ERR_UNSUPPORTED
+ * (there is no fused NV12 launch); fused = 2 plans the two dispatches.  The frame pipeline (fsr1_pipeline_*) does not take NV12. */
+int fsr1_upscale_ycbcr(const fsr1_image* in, const fsr1_image* intermediary, const fsr1_image* out, const fsr1_params* params,
+                       const fsr1_ycbcr* ycbcr, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Frame pipeline: independent frames on alternating HIP streams.
