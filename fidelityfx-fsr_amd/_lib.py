@@ -64,9 +64,15 @@ class fsr1_ycbcr(ctypes.Structure):
     ]
 
 
+class fsr1_rgb2ycbcr(ctypes.Structure):
+    """struct fsr1_rgb2ycbcr of include/fsr1_hip.h."""
+    _fields_ = fsr1_ycbcr._fields_
+
+
 _IMG = ctypes.POINTER(fsr1_image)
 _STG = ctypes.POINTER(fsr1_color_stages)
 _YCC = ctypes.POINTER(fsr1_ycbcr)
+_R2Y = ctypes.POINTER(fsr1_rgb2ycbcr)
 
 # name -> (restype, argtypes); every symbol include/fsr1_hip.h declares
 SYMBOLS = {
@@ -91,6 +97,10 @@ SYMBOLS = {
     "fsr1_ycbcr_bt709": (ctypes.c_int, [_YCC, ctypes.c_int]),
     "fsr1_easu_dispatch_ycbcr": (ctypes.c_int, [_IMG, _IMG, _U32P, _YCC, ctypes.c_uint32, ctypes.c_void_p]),
     "fsr1_upscale_ycbcr": (ctypes.c_int, [_IMG] * 3 + [ctypes.POINTER(fsr1_params), _YCC, ctypes.c_void_p]),
+    "fsr1_rgb2ycbcr_bt601": (ctypes.c_int, [_R2Y, ctypes.c_int]),
+    "fsr1_rgb2ycbcr_bt709": (ctypes.c_int, [_R2Y, ctypes.c_int]),
+    "fsr1_rcas_dispatch_ycbcr": (ctypes.c_int, [_IMG, _IMG, _U32P, _R2Y, ctypes.c_uint32, ctypes.c_void_p]),
+    "fsr1_transcode_ycbcr": (ctypes.c_int, [_IMG] * 3 + [ctypes.POINTER(fsr1_params), _YCC, _R2Y, ctypes.c_void_p]),
     "fsr1_pipeline_create": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int32]),
     "fsr1_pipeline_upscale": (ctypes.c_int, [ctypes.c_void_p, _IMG, _IMG, ctypes.POINTER(fsr1_params), _STG]),
     "fsr1_pipeline_reserve": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t]),

@@ -12,7 +12,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import Fsr1Error, fsr1_color_stages, fsr1_image, fsr1_params, fsr1_ycbcr  # noqa: F401
+from ._lib import Fsr1Error, fsr1_color_stages, fsr1_image, fsr1_params, fsr1_rgb2ycbcr, fsr1_ycbcr  # noqa: F401
 
 FORMAT_RGBA16F = 0
 FORMAT_RGBA32F = 1
@@ -27,7 +27,7 @@ FORMAT_RGB8_UNORM = 10  # the (H,W,3) uint8 frame of a decoder or an OpenCV / PI
 FORMAT_R16F = 11  # one channel (luma / greyscale): a (H,W), (N,H,W) or (N,1,H,W) tensor, marked with Mono()
 FORMAT_R32F = 12
 FORMAT_R8_UNORM = 13  # the Y plane of a decoded frame
-FORMAT_NV12 = 14  # a decoder's surface: 8-bit Y plane + interleaved CbCr plane, marked with Nv12(); input of easu(ycbcr=) / upscale_ycbcr only
+FORMAT_NV12 = 14  # a decoder's surface: 8-bit Y plane + interleaved CbCr plane, marked with Nv12(); input of easu(ycbcr=) / upscale_ycbcr / transcode_ycbcr, output of rcas(ycbcr=) / transcode_ycbcr
 
 CHROMA_REPLICATE = 0  # fsr1_ycbcr.siting (include/fsr1_hip.h)
 CHROMA_LEFT = 1       # H.264 / HEVC default: co-sited horizontally, centred vertically
@@ -224,7 +224,8 @@ class Nv12:
     """Marks a CUDA uint8 tensor shaped (rows, W) or (N, rows, W) as a decoded NV12 surface (FORMAT_NV12) as torch sees it: `height`
     rows of Y, then — from row rows - ch, ch = (height + 1) // 2 — the rows of interleaved Cb, Cr pairs; rows between the two (a
     surface whose height is aligned) are skipped.  height defaults to rows * 2 // 3, the tight surface.  Dense along x; the row stride
-    must hold the (W + 1) // 2 chroma pairs, so an odd W needs a padded row.  An input of easu(..., ycbcr=) and upscale_ycbcr only."""
+    must hold the (W + 1) // 2 chroma pairs, so an odd W needs a padded row.  An input of easu(..., ycbcr=YCbCr), upscale_ycbcr and transcode_ycbcr, and the output of
+    rcas(..., ycbcr=RgbToYCbCr) and transcode_ycbcr, which write the Y bytes and the pair bytes and nothing else of the tensor."""
 
     def __init__(self, t, height=None):
         self.t, self.height = t, height
@@ -257,7 +258,8 @@ class Nv12:
         return self._surface()[0]
 
     def chroma_offset_bytes(self):
-        """Bytes from the first Y byte of a frame to its first Cb byte: what fsr1_ycbcr.chroma_offset_bytes must say for this surface."""
+        """Bytes from the first Y byte of a frame to its first Cb byte: what fsr1_ycbcr / fsr1_rgb2ycbcr.chroma_offset_bytes must say for this
+        surface."""
         return self._surface()[1]
 
 
@@ -286,6 +288,40 @@ class YCbCr:
 
     def c_struct(self, chroma_offset_bytes=0):
         y = fsr1_ycbcr()
+        for r in range(3):
+            for c in range(3):
+                y.m[r][c] = float(self.m[r, c])
+            y.bias[r] = float(self.bias[r])
+        y.siting, y.chroma_offset_bytes = self.siting, int(chroma_offset_bytes)
+        return y
+
+
+class RgbToYCbCr:
+    """fsr1_rgb2ycbcr: the matrix (RGB in {0 to 1} in, codes 0..255 out), bias and chroma siting (CHROMA_CENTER: the 2 x 2 box, or
+    CHROMA_REPLICATE: the top-left pixel) of the NV12 store pinned in include/fsr1_hip.h.  RgbToYCbCr.bt601(full_range=False) /
+    RgbToYCbCr.bt709(...) fill the standard coefficients."""
+
+    def __init__(self, m, bias, siting=CHROMA_CENTER):
+        self.m = np.asarray(m, np.float32).reshape(3, 3)
+        self.bias = np.asarray(bias, np.float32).reshape(3)
+        self.siting = int(siting)
+
+    @classmethod
+    def _standard(cls, fill, full_range, siting):
+        y = fsr1_rgb2ycbcr()
+        _lib.check(getattr(_lib.load(), fill)(ctypes.byref(y), int(bool(full_range))))
+        return cls([list(r) for r in y.m], list(y.bias), siting)
+
+    @classmethod
+    def bt601(cls, full_range=False, siting=CHROMA_CENTER):
+        return cls._standard("fsr1_rgb2ycbcr_bt601", full_range, siting)
+
+    @classmethod
+    def bt709(cls, full_range=False, siting=CHROMA_CENTER):
+        return cls._standard("fsr1_rgb2ycbcr_bt709", full_range, siting)
+
+    def c_struct(self, chroma_offset_bytes=0):
+        y = fsr1_rgb2ycbcr()
         for r in range(3):
             for c in range(3):
                 y.m[r][c] = float(self.m[r, c])
@@ -422,11 +458,31 @@ def upscale_ycbcr(src, mid, dst, ycbcr, sharpness=0.25, use_rcas=True, fused=0, 
     return dst
 
 
-def rcas(src, dst, con=None, sharpness=0.25, flags=0, stream=None, stages=None):
-    """dst = RCAS(src); con defaults to FsrRcasCon(sharpness).  stages: optional ColorStages fused in."""
+def transcode_ycbcr(src, mid, dst, ycbcr_in, ycbcr_out, sharpness=0.25, fused=0, flags=0, hdr=False, stream=None, render_size=None, use_rcas=True):
+    """Nv12 dst = Upscale(Nv12 src) (fsr1_transcode_ycbcr): the NV12 EASU into `mid` — a Planar tensor of dst's size and any of the three
+    dtypes — then RCAS with the NV12 store.  ycbcr_in: YCbCr, ycbcr_out: RgbToYCbCr.  fused: 0 or 2; 1 and use_rcas=False are refused."""
+    i, o = image_of(src), image_of(dst)
+    m = image_of(mid) if mid is not None else None
+    rw, rh = render_size if render_size is not None else (i.width, i.height)
+    p = fsr1_params(float(rw), float(rh), int(bool(use_rcas)), float(sharpness), int(bool(hdr)), int(fused), int(flags))
+    yi = ycbcr_in.c_struct(src.chroma_offset_bytes() if isinstance(src, Nv12) else 0)
+    yo = ycbcr_out.c_struct(dst.chroma_offset_bytes() if isinstance(dst, Nv12) else 0)
+    _lib.check(_lib.load().fsr1_transcode_ycbcr(ctypes.byref(i), ctypes.byref(m) if m is not None else None, ctypes.byref(o), ctypes.byref(p),
+                                                ctypes.byref(yi), ctypes.byref(yo), _stream_ptr(stream)))
+    return dst
+
+
+def rcas(src, dst, con=None, sharpness=0.25, flags=0, stream=None, stages=None, ycbcr=None):
+    """dst = RCAS(src); con defaults to FsrRcasCon(sharpness).  stages: optional ColorStages fused in.
+    ycbcr: the RgbToYCbCr conversion of an Nv12 destination (src is then a Planar tensor of any of its three dtypes): fsr1_rcas_dispatch_ycbcr."""
     i, o = image_of(src), image_of(dst)
     con = _con(FsrRcasCon(sharpness) if con is None else con, 4)
-    if stages is None:
+    if ycbcr is not None:
+        if stages is not None:
+            raise Fsr1Error("colour stages are not built for NV12 images")
+        y = ycbcr.c_struct(dst.chroma_offset_bytes() if isinstance(dst, Nv12) else 0)
+        _lib.check(_lib.load().fsr1_rcas_dispatch_ycbcr(ctypes.byref(i), ctypes.byref(o), _u32p(con), ctypes.byref(y), flags, _stream_ptr(stream)))
+    elif stages is None:
         _lib.check(_lib.load().fsr1_rcas_dispatch(ctypes.byref(i), ctypes.byref(o), _u32p(con), flags, _stream_ptr(stream)))
     else:
         sp, _keep = _stages(stages)

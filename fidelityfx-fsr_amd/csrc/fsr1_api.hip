@@ -54,6 +54,7 @@ size_t easu_mono_lds_bytes(int fp_w, int fp_h);
 hipError_t rcas_mono_launch(const RcasArgs& a, int fmt, bool exact, bool wide, hipStream_t stream);
 void rcas_mono_geometry(int fmt, int width, int height, int frames, bool overlapped, int cus, int* tiles_x, int* tiles_y, int* rows);
 size_t rcas_mono_access_bytes(int fmt);
+hipError_t rcas_nv12_launch(const RcasArgs& a, const fsr1_rgb2ycbcr& yc, long long chroma_offset, int fin, bool exact, bool wide, hipStream_t stream);
 hipError_t easu_nv12_launch(const EasuArgs& a, const fsr1_ycbcr& ycbcr, long long chroma_offset, int fout, bool exact, bool s2, bool wide, hipStream_t stream);
 size_t easu_nv12_lds_bytes(int fp_w, int fp_h);
 }  // namespace fsr1
@@ -165,9 +166,9 @@ static size_t pixel_bytes(int fmt) {
   return fmt == FSR1_FORMAT_RGBA32F ? 16 : (fmt == FSR1_FORMAT_RGBA16F ? 8 : 4);
 }
 
-// NV12 (fsr1_hip.h) is an input of fsr1_easu_dispatch_ycbcr / fsr1_upscale_ycbcr alone: what every other entry point answers
+// NV12 (fsr1_hip.h) is an input and an output of the *_ycbcr entry points alone: what every other entry point answers
 static int nv12_refusal(const char* name) {
-  return fail(FSR1_ERR_UNSUPPORTED, "%s: NV12 images are an input of fsr1_easu_dispatch_ycbcr / fsr1_upscale_ycbcr only", name);
+  return fail(FSR1_ERR_UNSUPPORTED, "%s: NV12 images are served by the fsr1_*_ycbcr entry points only", name);
 }
 
 static bool any_nv12(const fsr1_image* a, const fsr1_image* b) { return (a && a->format == FSR1_FORMAT_NV12) || (b && b->format == FSR1_FORMAT_NV12); }
@@ -1035,22 +1036,23 @@ int fsr1_upscale_plan(const fsr1_image* in, int32_t have_intermediary, const fsr
 // ---- NV12 in, planar RGB out (include/fsr1_hip.h, fsr1_easu_nv12.hip) ----
 // An NV12 descriptor and its fsr1_ycbcr -> the view of the Y plane (whose pitch and frame stride the chroma plane shares), the resolved
 // chroma offset and the bytes of one frame.  check_image's rules with the element being a Cb, Cr pair: multiples of 2 everywhere.
-static int check_nv12(const fsr1_image* im, const fsr1_ycbcr* yc, const char* name, ImageView* v, long long* chroma_offset, long long* frame_bytes) {
+// conv / conv_name: the caller's fsr1_ycbcr (an input) or fsr1_rgb2ycbcr (an output), of which siting_ok, siting and offset are its words.
+static int check_nv12(const fsr1_image* im, const void* conv, const char* conv_name, bool siting_ok, int siting, long long offset, const char* name,
+                      const char* role, ImageView* v, long long* chroma_offset, long long* frame_bytes) {
   if (!im) return fail(FSR1_ERR_INVALID_ARGUMENT, "%s: null image descriptor", name);
-  if (im->format != FSR1_FORMAT_NV12) return fail(FSR1_ERR_UNSUPPORTED, "%s: the input must be FSR1_FORMAT_NV12, got format %d", name, im->format);
-  if (!yc) return fail(FSR1_ERR_INVALID_ARGUMENT, "%s: null fsr1_ycbcr", name);
+  if (im->format != FSR1_FORMAT_NV12) return fail(FSR1_ERR_UNSUPPORTED, "%s: the %s must be FSR1_FORMAT_NV12, got format %d", name, role, im->format);
+  if (!conv) return fail(FSR1_ERR_INVALID_ARGUMENT, "%s: null %s", name, conv_name);
   if (!im->data) return fail(FSR1_ERR_INVALID_ARGUMENT, "%s: null data pointer", name);
   if (im->width <= 0 || im->height <= 0 || im->frames <= 0)
     return fail(FSR1_ERR_INVALID_ARGUMENT, "%s: bad extent %dx%dx%d", name, im->width, im->height, im->frames);
   if (im->width > (1 << 20) || im->height > (1 << 20))
     return fail(FSR1_ERR_UNSUPPORTED, "%s: extent %dx%d beyond 2^20 pixels per side", name, im->width, im->height);
-  if (yc->siting != FSR1_CHROMA_REPLICATE && yc->siting != FSR1_CHROMA_LEFT && yc->siting != FSR1_CHROMA_CENTER)
-    return fail(FSR1_ERR_UNSUPPORTED, "%s: unknown NV12 chroma siting %d", name, yc->siting);
+  if (!siting_ok) return fail(FSR1_ERR_UNSUPPORTED, "%s: %s NV12 chroma siting %d", name, siting == FSR1_CHROMA_LEFT ? "unsupported" : "unknown", siting);
   const long long cw = (im->width + 1) / 2, ch = (im->height + 1) / 2;
   const long long pitch = im->row_pitch_bytes ? im->row_pitch_bytes : 2 * cw;
   if (pitch < 2 * cw || pitch % 2)
     return fail(FSR1_ERR_INVALID_ARGUMENT, "%s: NV12 row pitch %lld must be even and hold %lld bytes of chroma pairs", name, pitch, 2 * cw);
-  const long long coff = yc->chroma_offset_bytes ? yc->chroma_offset_bytes : pitch * im->height;
+  const long long coff = offset ? offset : pitch * im->height;
   if (coff < pitch * im->height || coff % 2 || coff > (1ll << 40))
     return fail(FSR1_ERR_INVALID_ARGUMENT, "%s: NV12 chroma offset %lld must be even and at least pitch x height = %lld", name, coff, pitch * im->height);
   const long long fbytes = coff + pitch * ch;
@@ -1077,8 +1079,11 @@ int fsr1_easu_dispatch_ycbcr(const fsr1_image* in, const fsr1_image* out, const 
   memset(&a.color, 0, sizeof a.color);
   long long chroma_offset = 0, frame_bytes = 0;
   if (int rc = check_flags(flags)) return rc;
-  if (int rc = check_nv12(in, ycbcr, "easu_ycbcr input", &a.in, &chroma_offset, &frame_bytes)) return rc;
-  if (out && out->format == FSR1_FORMAT_NV12) return fail(FSR1_ERR_UNSUPPORTED, "easu_ycbcr output: NV12 as an output is not built");
+  const bool siting_ok = ycbcr && (ycbcr->siting == FSR1_CHROMA_REPLICATE || ycbcr->siting == FSR1_CHROMA_LEFT || ycbcr->siting == FSR1_CHROMA_CENTER);
+  if (int rc = check_nv12(in, ycbcr, "fsr1_ycbcr", siting_ok, ycbcr ? ycbcr->siting : 0, ycbcr ? ycbcr->chroma_offset_bytes : 0, "easu_ycbcr input", "input",
+                          &a.in, &chroma_offset, &frame_bytes))
+    return rc;
+  if (out && out->format == FSR1_FORMAT_NV12) return fail(FSR1_ERR_UNSUPPORTED, "easu_ycbcr output: there is no EASU with an NV12 store (fsr1_rcas_dispatch_ycbcr has one)");
   if (int rc = check_image(out, "easu_ycbcr output", &a.out)) return rc;
   if (!is_planar(out->format))
     return fail(FSR1_ERR_UNSUPPORTED, "easu_ycbcr: an NV12 input needs a planar output (RGB16F_PLANAR, RGB32F_PLANAR or RGB8_UNORM_PLANAR), got format %d", out->format);
@@ -1132,6 +1137,81 @@ int fsr1_upscale_ycbcr(const fsr1_image* in, const fsr1_image* intermediary, con
   if (int rc = fsr1_easu_dispatch_ycbcr(in, intermediary, easu_con, ycbcr, math, stream)) return rc;  // :121
   FsrRcasCon(rcas_con, p->rcas_attenuation);                                                          // :124
   return fsr1_rcas_dispatch(intermediary, out, rcas_con, math | rcas_opts | out_policy | (p->hdr ? FSR1_FLAG_HDR_SQUARE : 0u), stream);  // :131
+}
+
+// ---- planar RGB in, NV12 out (include/fsr1_hip.h, fsr1_rcas_nv12.hip) ----
+int fsr1_rcas_dispatch_ycbcr(const fsr1_image* in, const fsr1_image* out, const uint32_t con[4], const fsr1_rgb2ycbcr* yc, uint32_t flags, void* stream) {
+  const Range range("rcas_ycbcr", in, out);
+  RcasArgs a;
+  a.xcd_shift = device_xcd_shift();
+  memset(&a.color, 0, sizeof a.color);
+  long long chroma_offset = 0, frame_bytes = 0;
+  if (int rc = check_flags(flags)) return rc;
+  if (in && !is_planar(in->format))
+    return fail(FSR1_ERR_UNSUPPORTED, "rcas_ycbcr: an NV12 output needs a planar input (RGB16F_PLANAR, RGB32F_PLANAR or RGB8_UNORM_PLANAR), got format %d", in->format);
+  if (int rc = check_image(in, "rcas_ycbcr input", &a.in)) return rc;
+  const bool siting_ok = yc && (yc->siting == FSR1_CHROMA_REPLICATE || yc->siting == FSR1_CHROMA_CENTER);
+  if (int rc = check_nv12(out, yc, "fsr1_rgb2ycbcr", siting_ok, yc ? yc->siting : 0, yc ? yc->chroma_offset_bytes : 0, "rcas_ycbcr output", "output", &a.out,
+                          &chroma_offset, &frame_bytes))
+    return rc;
+  if (flags & FSR1_FLAG_MATH_PACKED_FP16) return fail(FSR1_ERR_UNSUPPORTED, "rcas_ycbcr: NV12 images run with the F (binary32) arithmetic, not packed fp16");
+  if (flags & FSR1_FLAG_RCAS_PASSTHROUGH_ALPHA) return fail(FSR1_ERR_UNSUPPORTED, "rcas_ycbcr: planar and NV12 images have no alpha to pass through");
+  if (!con) return fail(FSR1_ERR_INVALID_ARGUMENT, "rcas_ycbcr: null constants");
+  if (in->width != out->width || in->height != out->height || in->frames != out->frames)
+    return fail(FSR1_ERR_INVALID_ARGUMENT, "rcas_ycbcr: input %dx%dx%d and output %dx%dx%d extents differ", in->width, in->height, in->frames, out->width,
+                out->height, out->frames);
+  {  // the overlap test of the other dispatches, over what an NV12 batch occupies: its last frame ends behind its chroma plane
+    const char* const i0 = a.in.base;
+    const char* const i1 = a.in.base + a.in.frame_stride * (in->frames - 1) + a.in.pitch * in->height * image_planes(in->format);
+    const char* const o0 = a.out.base;
+    const char* const o1 = a.out.base + a.out.frame_stride * (out->frames - 1) + frame_bytes;
+    if (i0 < o1 && o0 < i1) return fail(FSR1_ERR_INVALID_ARGUMENT, "rcas_ycbcr: input and output overlap (RCAS cannot run in place)");
+  }
+  memcpy(a.con, con, sizeof a.con);
+  rcas_planar_geometry(out->width, out->height, out->frames, (flags & FSR1_FLAG_FRAMES_OVERLAP) != 0, &a.tiles_x, &a.tiles_y, &a.rows);
+  a.frames = out->frames;
+  if (int rc = check_grid("rcas_ycbcr", a.tiles_x, a.tiles_y, a.frames)) return rc;
+  a.flags = resolve_output_policy(flags, true);
+  a.rows_above = a.rows_below = 0;
+  // the input by the planar rule; the surface: dword stores into both planes
+  const bool wide = planar_aligned(in, a.in, 4 * pixel_bytes(in->format)) && (uintptr_t)a.out.base % 4 == 0 && a.out.pitch % 4 == 0 && chroma_offset % 4 == 0 &&
+                    a.out.frame_stride % 4 == 0;
+  const bool exact = (flags & (FSR1_FLAG_MATH_EXACT | FSR1_FLAG_MATH_STRICT)) != 0;
+  if (const hipError_t e = rcas_nv12_launch(a, *yc, chroma_offset, in->format, exact, wide, static_cast<hipStream_t>(stream)); e != hipSuccess)
+    return hip_fail(e, "rcas_ycbcr launch");
+  return FSR1_OK;
+}
+
+// Decode -> upscale -> encode: fsr1_upscale_ycbcr's road with the NV12 store behind RCAS.
+int fsr1_transcode_ycbcr(const fsr1_image* in, const fsr1_image* intermediary, const fsr1_image* out, const fsr1_params* p, const fsr1_ycbcr* ycbcr_in,
+                         const fsr1_rgb2ycbcr* ycbcr_out, void* stream) {
+  const Range range("transcode_ycbcr", in, out);
+  if (!in || !out || !p) return fail(FSR1_ERR_INVALID_ARGUMENT, "transcode_ycbcr: null argument");
+  if (in->format != FSR1_FORMAT_NV12 || out->format != FSR1_FORMAT_NV12)
+    return fail(FSR1_ERR_UNSUPPORTED, "transcode_ycbcr: input and output must be FSR1_FORMAT_NV12, got formats %d -> %d", in->format, out->format);
+  if (int rc = check_flags(p->flags)) return rc;
+  const uint32_t math = p->flags & (FSR1_FLAG_MATH_EXACT | FSR1_FLAG_MATH_PACKED_FP16 | FSR1_FLAG_MATH_STRICT | FSR1_FLAG_NO_FAST_PATHS | FSR1_FLAG_FRAMES_OVERLAP);
+  const uint32_t rcas_opts = p->flags & FSR1_FLAG_RCAS_DENOISE;
+  const uint32_t out_policy = p->flags & (FSR1_FLAG_OUTPUT_STREAMING | FSR1_FLAG_OUTPUT_CACHED);  // of the pass that writes `out`
+  if (p->flags & ~(math | rcas_opts | out_policy))
+    return fail(FSR1_ERR_INVALID_ARGUMENT, "transcode_ycbcr: params.flags may only hold MATH_*, RCAS_DENOISE, OUTPUT_* and FRAMES_OVERLAP bits");
+  if (!p->use_rcas) return fail(FSR1_ERR_UNSUPPORTED, "transcode_ycbcr: the NV12 store is RCAS's; there is no EASU with an NV12 output (use_rcas = 0)");
+  if (p->fused != 0 && p->fused != 1 && p->fused != 2) return fail(FSR1_ERR_INVALID_ARGUMENT, "transcode_ycbcr: params.fused must be 0, 1 or 2 (auto)");
+  if (p->fused == 1 || !intermediary)
+    return fail(FSR1_ERR_UNSUPPORTED, "transcode_ycbcr: NV12 images run as two dispatches; pass an intermediary and fused = 0 or 2");
+  if (!is_planar(intermediary->format))
+    return fail(FSR1_ERR_UNSUPPORTED, "transcode_ycbcr: between the NV12 images the intermediary must be planar, got format %d", intermediary->format);
+  if (in->width <= 0 || in->height <= 0 || out->width <= 0 || out->height <= 0)
+    return fail(FSR1_ERR_INVALID_ARGUMENT, "transcode_ycbcr: bad extent %dx%d -> %dx%d", in->width, in->height, out->width, out->height);
+  if (!(p->render_width >= 1.0f) || !(p->render_height >= 1.0f) || p->render_width > (float)in->width || p->render_height > (float)in->height)
+    return fail(FSR1_ERR_INVALID_ARGUMENT, "transcode_ycbcr: render size %gx%g must lie within the input image %dx%d", (double)p->render_width,
+                (double)p->render_height, in->width, in->height);
+  uint32_t easu_con[16], rcas_con[4];
+  FsrEasuCon(easu_con, easu_con + 4, easu_con + 8, easu_con + 12, p->render_width, p->render_height, p->render_width, p->render_height,
+             (float)out->width, (float)out->height);  // FSR_Filter.cpp:106
+  if (int rc = fsr1_easu_dispatch_ycbcr(in, intermediary, easu_con, ycbcr_in, math, stream)) return rc;  // :121
+  FsrRcasCon(rcas_con, p->rcas_attenuation);                                                             // :124
+  return fsr1_rcas_dispatch_ycbcr(intermediary, out, rcas_con, ycbcr_out, math | rcas_opts | out_policy | (p->hdr ? FSR1_FLAG_HDR_SQUARE : 0u), stream);  // :131
 }
 
 int fsr1_selftest(uint32_t* failures) {

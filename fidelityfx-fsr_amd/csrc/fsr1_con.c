@@ -107,3 +107,24 @@ static int ycbcr_fill(fsr1_ycbcr* y, double kr, double kb, int full_range) {
 
 int fsr1_ycbcr_bt601(fsr1_ycbcr* ycbcr, int full_range) { return ycbcr_fill(ycbcr, 0.299, 0.114, full_range); }
 int fsr1_ycbcr_bt709(fsr1_ycbcr* ycbcr, int full_range) { return ycbcr_fill(ycbcr, 0.2126, 0.0722, full_range); }
+
+/* RGB -> YCbCr matrices for RGB in {0 to 1} in, codes 0 .. 255 out (fsr1_rgb2ycbcr, include/fsr1_hip.h), from the same Kr, Kb:
+ *   Y = y0 + ys (Kr R + Kg G + Kb B),  Cb = 128 + cs (B - E'y) / (2 (1 - Kb)),  Cr = 128 + cs (R - E'y) / (2 (1 - Kr))
+ * with E'y = Kr R + Kg G + Kb B.  Every coefficient is formed in double and rounded to float once. */
+static int rgb2ycbcr_fill(fsr1_rgb2ycbcr* y, double kr, double kb, int full_range) {
+  if (!y) return FSR1_ERR_INVALID_ARGUMENT;
+  const double kg = 1.0 - kr - kb;
+  const double y0 = full_range ? 0.0 : 16.0, ys = full_range ? 255.0 : 219.0, cs = full_range ? 255.0 : 224.0;
+  const double cb = cs / (2.0 * (1.0 - kb)), cr = cs / (2.0 * (1.0 - kr));
+  const double m[3][3] = {{ys * kr, ys * kg, ys * kb}, {-cb * kr, -cb * kg, cb * (1.0 - kb)}, {cr * (1.0 - kr), -cr * kg, -cr * kb}};
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c) y->m[r][c] = (float)m[r][c];
+    y->bias[r] = (float)(r ? 128.0 : y0);
+  }
+  y->siting = FSR1_CHROMA_CENTER;
+  y->chroma_offset_bytes = 0;
+  return FSR1_OK;
+}
+
+int fsr1_rgb2ycbcr_bt601(fsr1_rgb2ycbcr* ycbcr, int full_range) { return rgb2ycbcr_fill(ycbcr, 0.299, 0.114, full_range); }
+int fsr1_rgb2ycbcr_bt709(fsr1_rgb2ycbcr* ycbcr, int full_range) { return rgb2ycbcr_fill(ycbcr, 0.2126, 0.0722, full_range); }

@@ -134,19 +134,21 @@ typedef enum fsr1_format {
   FSR1_FORMAT_R16F = 11,              /* binary16, 2 B/pixel */
   FSR1_FORMAT_R32F = 12,              /* binary32, 4 B/pixel */
   FSR1_FORMAT_R8_UNORM = 13,          /* 8-bit UNORM, 1 B/pixel */
-  /* NV12 — 4:2:0 YCbCr as a hardware decoder writes it — INPUT ONLY, and only of fsr1_easu_dispatch_ycbcr / fsr1_upscale_ycbcr
-   * (below, with the pinned conversion); every other entry point, and NV12 as an output, is FSR1_ERR_UNSUPPORTED with "NV12" in the
-   * message.  A frame is a full-resolution plane of 8-bit Y codes followed by a plane of interleaved (Cb, Cr) byte pairs at half the
-   * resolution each way.  fsr1_image describes it unchanged:
+  /* NV12 — 4:2:0 YCbCr as a hardware decoder writes it and an encoder reads it.  The INPUT of fsr1_easu_dispatch_ycbcr /
+   * fsr1_upscale_ycbcr / fsr1_transcode_ycbcr and the OUTPUT of fsr1_rcas_dispatch_ycbcr / fsr1_transcode_ycbcr (below, with the
+   * pinned conversions); anywhere else it is FSR1_ERR_UNSUPPORTED with "NV12" in the message.  A frame is a full-resolution plane of
+   * 8-bit Y codes followed by a plane of interleaved (Cb, Cr) byte pairs at half the resolution each way.  fsr1_image describes it
+   * unchanged, as an input and as an output alike:
    *   width / height      the LUMA size, any size >= 1, odd included; the chroma plane is cw = (width + 1) / 2 pairs by
    *                       ch = (height + 1) / 2 rows
    *   row_pitch_bytes     shared by both planes; 0 = 2 * cw (= width rounded up to even); it must hold 2 * cw bytes (and with them
    *                       the `width` bytes of a Y row)
-   *   the chroma plane    starts fsr1_ycbcr.chroma_offset_bytes after `data` (0 = pitch * height: directly behind the last Y row;
-   *                       otherwise >= that — a surface whose height is aligned keeps it at pitch * aligned height)
+   *   the chroma plane    starts fsr1_ycbcr.chroma_offset_bytes (an output: fsr1_rgb2ycbcr.chroma_offset_bytes) after `data` (0 = pitch *
+   *                       height: directly behind the last Y row; otherwise >= that — a surface whose height is aligned keeps it
+   *                       at pitch * aligned height)
    *   frame_stride_bytes  0 = chroma offset + pitch * ch
-   * Pointer, pitch, chroma offset and frame stride need only be multiples of 2: the kernel reads Y bytes and 16-bit pairs, nothing
-   * wider, whatever the alignment. */
+   * Pointer, pitch, chroma offset and frame stride need only be multiples of 2: the kernels read and write Y bytes and 16-bit pairs,
+   * nothing wider, unless all four are multiples of 4 (an output then takes dword stores). */
   FSR1_FORMAT_NV12 = 14               /* 8-bit Y plane + interleaved CbCr plane, 1.5 B/pixel */
 } fsr1_format;
 
@@ -450,6 +452,56 @@ int fsr1_easu_dispatch_ycbcr(const fsr1_image* in, const fsr1_image* out, const 
  * (there is no fused NV12 launch); fused = 2 plans the two dispatches.  The frame pipeline (fsr1_pipeline_*) does not take NV12. */
 int fsr1_upscale_ycbcr(const fsr1_image* in, const fsr1_image* intermediary, const fsr1_image* out, const fsr1_params* params,
                        const fsr1_ycbcr* ycbcr, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Planar RGB in, NV12 out: RCAS converts and decimates in its store — the sharpened image never exists as RGB in memory.
+ *
+ * THE PINNED CONVERSION, RGB -> NV12 (the parity contract of the output side).  p(x, y) is the binary32 RGB value RCAS computes for
+ * output pixel (x, y): the value the planar binary32 kernel stores for the same input and flags, bit for bit (FSR1_FLAG_RCAS_DENOISE
+ * and FSR1_FLAG_HDR_SQUARE act exactly as there; no RGB clamp is added).  Every product and every sum below is rounded to binary32 BY
+ * ITSELF, round-to-nearest-even, never contracted into a fused multiply-add, in every arithmetic mode.
+ *   Luma, per pixel, from p(x, y) = (R, G, B):
+ *     v = bias[0] + m[0][0] * R
+ *     v = v + m[0][1] * G
+ *     v = v + m[0][2] * B
+ *   Chroma, per 2 x 2 block (k, j), 0 <= k < cw, 0 <= j < ch, per channel of R, G, B FIRST; x and y indices are clamped to the image, so
+ *   an odd last column or row stands in for its missing neighbour:
+ *     FSR1_CHROMA_CENTER     s0 = p(2k, 2j) + p(2k + 1, 2j);  s1 = p(2k, 2j + 1) + p(2k + 1, 2j + 1);  a = 0.25 * (s0 + s1)
+ *                            (the box of libyuv-style converters: three roundings in this order, the scaling is exact)
+ *     FSR1_CHROMA_REPLICATE  a = p(2k, 2j)  (co-sited top-left: plain decimation)
+ *     FSR1_CHROMA_LEFT       refused: it needs p(2k - 1, .), which for a wave's first lane is another wave's result
+ *   then Cb and Cr from a = (R, G, B) with rows 1 and 2 of m and bias, in the three-step form of luma.
+ *   Code, for Y, Cb and Cr alike:  (uint8)(min(max(v, 0), 255) + 0.5f) — one rounded addition, then truncation; NaN stores 0 (the
+ *   UNORM store rule above, in code units).
+ *   No byte outside the width x height Y bytes and the 2 cw x ch pair bytes of a frame is ever written.
+ * A binary32 restatement of these lines (numpy float32) on the planar binary32 RCAS result reproduces the surface byte for byte,
+ * default arithmetic included.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct fsr1_rgb2ycbcr {
+  float m[3][3];               /* rows Y, Cb, Cr; columns R, G, B: RGB in {0 to 1} in, codes 0 .. 255 out */
+  float bias[3];
+  int32_t siting;              /* FSR1_CHROMA_CENTER or FSR1_CHROMA_REPLICATE */
+  int64_t chroma_offset_bytes; /* as in fsr1_ycbcr: 0 = pitch * height */
+} fsr1_rgb2ycbcr;
+
+/* Fill m and bias for ITU-R BT.601 / BT.709, limited or full range, computed in double from Kr / Kb and rounded once to float.
+ * siting = FSR1_CHROMA_CENTER, chroma_offset_bytes = 0.  Host, pure. */
+int fsr1_rgb2ycbcr_bt601(fsr1_rgb2ycbcr* rgb2ycbcr, int full_range);
+int fsr1_rgb2ycbcr_bt709(fsr1_rgb2ycbcr* rgb2ycbcr, int full_range);
+
+/* RCAS of a planar RGB image (any of the three planar formats) into an NV12 image of the same extent.  The planar RCAS dispatch's
+ * validation, the NV12 rules above for `out`, the overlap test over what an NV12 batch occupies; default F arithmetic or
+ * FSR1_FLAG_MATH_EXACT, FSR1_FLAG_MATH_STRICT takes EXACT as for planar; RCAS_DENOISE, HDR_SQUARE, OUTPUT_* and FRAMES_OVERLAP as for
+ * planar.  FSR1_ERR_UNSUPPORTED ("NV12" in the message): an input that is not planar, an output that is not NV12,
+ * FSR1_FLAG_MATH_PACKED_FP16, FSR1_FLAG_RCAS_PASSTHROUGH_ALPHA, siting LEFT or unknown. */
+int fsr1_rcas_dispatch_ycbcr(const fsr1_image* in, const fsr1_image* out, const uint32_t con[4], const fsr1_rgb2ycbcr* rgb2ycbcr,
+                             uint32_t flags, void* stream);
+
+/* Decode -> upscale -> encode: NV12 in, fsr1_easu_dispatch_ycbcr into a planar intermediary of any of the three types and out's
+ * extent, fsr1_rcas_dispatch_ycbcr into the NV12 `out`.  fsr1_upscale_ycbcr's parameter rules; use_rcas == 0 (there is no EASU with an
+ * NV12 store), fused == 1 and a missing intermediary are FSR1_ERR_UNSUPPORTED ("NV12" in the message). */
+int fsr1_transcode_ycbcr(const fsr1_image* in, const fsr1_image* intermediary, const fsr1_image* out, const fsr1_params* params,
+                         const fsr1_ycbcr* ycbcr_in, const fsr1_rgb2ycbcr* ycbcr_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Frame pipeline: independent frames on alternating HIP streams.
