@@ -95,10 +95,12 @@ SYMBOLS = {
     "fsr1_upscale_plan": (ctypes.c_int, [_IMG, ctypes.c_int32, _IMG, ctypes.POINTER(fsr1_params), ctypes.c_int32]),
     "fsr1_ycbcr_bt601": (ctypes.c_int, [_YCC, ctypes.c_int]),
     "fsr1_ycbcr_bt709": (ctypes.c_int, [_YCC, ctypes.c_int]),
+    "fsr1_ycbcr_fill": (ctypes.c_int, [_YCC, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "fsr1_easu_dispatch_ycbcr": (ctypes.c_int, [_IMG, _IMG, _U32P, _YCC, ctypes.c_uint32, ctypes.c_void_p]),
     "fsr1_upscale_ycbcr": (ctypes.c_int, [_IMG] * 3 + [ctypes.POINTER(fsr1_params), _YCC, ctypes.c_void_p]),
     "fsr1_rgb2ycbcr_bt601": (ctypes.c_int, [_R2Y, ctypes.c_int]),
     "fsr1_rgb2ycbcr_bt709": (ctypes.c_int, [_R2Y, ctypes.c_int]),
+    "fsr1_rgb2ycbcr_fill": (ctypes.c_int, [_R2Y, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "fsr1_rcas_dispatch_ycbcr": (ctypes.c_int, [_IMG, _IMG, _U32P, _R2Y, ctypes.c_uint32, ctypes.c_void_p]),
     "fsr1_transcode_ycbcr": (ctypes.c_int, [_IMG] * 3 + [ctypes.POINTER(fsr1_params), _YCC, _R2Y, ctypes.c_void_p]),
     "fsr1_pipeline_create": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int32]),

@@ -28,6 +28,10 @@ FORMAT_R16F = 11  # one channel (luma / greyscale): a (H,W), (N,H,W) or (N,1,H,W
 FORMAT_R32F = 12
 FORMAT_R8_UNORM = 13  # the Y plane of a decoded frame
 FORMAT_NV12 = 14  # a decoder's surface: 8-bit Y plane + interleaved CbCr plane, marked with Nv12(); input of easu(ycbcr=) / upscale_ycbcr / transcode_ycbcr, output of rcas(ycbcr=) / transcode_ycbcr
+FORMAT_P010 = 15  # NV12's arrangement in 16-bit words, the 10-bit code in the upper bits: what a 10-bit / HDR10 decoder writes; marked with P010(), taken wherever Nv12() is
+FORMAT_P016 = 16  # the same with 16-bit codes, marked with P016()
+
+YCBCR_BT601, YCBCR_BT709, YCBCR_BT2020 = 0, 1, 2  # `standard` of fsr1_ycbcr_fill / fsr1_rgb2ycbcr_fill
 
 CHROMA_REPLICATE = 0  # fsr1_ycbcr.siting (include/fsr1_hip.h)
 CHROMA_LEFT = 1       # H.264 / HEVC default: co-sited horizontally, centred vertically
@@ -227,32 +231,39 @@ class Nv12:
     must hold the (W + 1) // 2 chroma pairs, so an odd W needs a padded row.  An input of easu(..., ycbcr=YCbCr), upscale_ycbcr and transcode_ycbcr, and the output of
     rcas(..., ycbcr=RgbToYCbCr) and transcode_ycbcr, which write the Y bytes and the pair bytes and nothing else of the tensor."""
 
+    NAME, FORMAT, ELEM = "NV12", FORMAT_NV12, 1  # ELEM: bytes of a code
+
     def __init__(self, t, height=None):
         self.t, self.height = t, height
 
-    def _surface(self):
+    def _dtypes(self):
         import torch
-        t = self.t
+        return (torch.uint8,)
+
+    def _surface(self):
+        t, name, es = self.t, self.NAME, self.ELEM
         if not t.is_cuda:
             raise Fsr1Error("image tensors must live on the GPU (got %s); there is no CPU path" % t.device)
-        if t.dtype != torch.uint8:
-            raise Fsr1Error("NV12 surfaces are uint8, got %s" % t.dtype)
+        if t.dtype not in self._dtypes():
+            raise Fsr1Error("%s surfaces are %s, got %s" % (name, " or ".join(str(d) for d in self._dtypes()), t.dtype))
         if t.dim() == 2:
             t = t.unsqueeze(0)
         if t.dim() != 3:
-            raise Fsr1Error("expected a (rows, W) or (N, rows, W) NV12 surface, got %s" % (tuple(self.t.shape),))
+            raise Fsr1Error("expected a (rows, W) or (N, rows, W) %s surface, got %s" % (name, tuple(self.t.shape)))
         n, rows, w = t.shape
         h = rows * 2 // 3 if self.height is None else int(self.height)
         ch = (h + 1) // 2
         if h < 1 or w < 1 or h + ch > rows:
-            raise Fsr1Error("an NV12 surface of height %d needs %d rows, the tensor has %d" % (h, h + ch, rows))
+            raise Fsr1Error("an %s surface of height %d needs %d rows, the tensor has %d" % (name, h, h + ch, rows))
         sn, sh, sw = t.stride()
         if sw != 1:
-            raise Fsr1Error("NV12 surfaces must be dense along x (got a stride of %d elements)" % sw)
+            raise Fsr1Error("%s surfaces must be dense along x (got a stride of %d elements)" % (name, sw))
         if sh < (w + 1) // 2 * 2:
-            raise Fsr1Error("row stride %d bytes cannot hold the %d chroma pairs of a %d-pixel row (pad the rows of an odd width)" % (sh, (w + 1) // 2, w))
+            raise Fsr1Error("row stride %d elements cannot hold the %d chroma pairs of a %d-pixel row (pad the rows of an odd width)" % (sh, (w + 1) // 2, w))
         _check_strides(n, rows, w, sn, sh, 1)
-        return fsr1_image(t.data_ptr(), w, h, FORMAT_NV12, n, sh, sn if n > 1 else 0), (rows - ch) * sh
+        if es == 2 and (t.data_ptr() % 4 or sh % 2 or (rows - ch) * sh % 2 or (n > 1 and sn % 2)):  # (in elements: a pair is two)
+            raise Fsr1Error("%s surfaces keep their pairs as aligned dwords: pointer, row stride, chroma offset and frame stride must be multiples of 4 bytes" % name)
+        return fsr1_image(t.data_ptr(), w, h, self.FORMAT, n, sh * es, sn * es if n > 1 else 0), (rows - ch) * sh * es
 
     def image(self):
         return self._surface()[0]
@@ -263,9 +274,28 @@ class Nv12:
         return self._surface()[1]
 
 
+class P010(Nv12):
+    """Marks a CUDA torch.int16 or torch.uint16 tensor shaped (rows, W) or (N, rows, W), in elements, as a P010 surface (FORMAT_P010):
+    Nv12's arrangement and validation in 16-bit words, the 10-bit code in the upper bits of a word (the low six bits of an input word
+    are ignored and stored as zero).  A (Cb, Cr) pair is one aligned dword, so pointer, row stride, chroma offset and frame stride must
+    be multiples of 4 bytes.  Taken wherever Nv12 is: easu(ycbcr=), upscale_ycbcr, rcas(ycbcr=), transcode_ycbcr — with conversions of
+    the format's depth (YCbCr.bt2020(bits=10), ...)."""
+    NAME, FORMAT, ELEM = "P010", FORMAT_P010, 2
+
+    def _dtypes(self):
+        import torch
+        return (torch.int16, torch.uint16)
+
+
+class P016(P010):
+    """P010 with 16-bit codes (FORMAT_P016): the word is the code.  Conversions of bits=16."""
+    NAME, FORMAT = "P016", FORMAT_P016
+
+
 class YCbCr:
-    """fsr1_ycbcr: the matrix (raw codes 0..255 in, RGB in {0 to 1} out), bias and chroma siting of the conversion pinned in
-    include/fsr1_hip.h.  YCbCr.bt601(full_range=False) / YCbCr.bt709(...) fill the standard coefficients."""
+    """fsr1_ycbcr: the matrix (raw codes 0..2^bits - 1 in, RGB in {0 to 1} out), bias and chroma siting of the conversion pinned in
+    include/fsr1_hip.h.  YCbCr.bt601(full_range=False) / YCbCr.bt709(...) / YCbCr.bt2020(...) fill the standard coefficients; bits = 8
+    (Nv12), 10 (P010), 12 or 16 (P016) is the depth of the codes (fsr1_ycbcr_fill)."""
 
     def __init__(self, m, bias, siting=CHROMA_LEFT):
         self.m = np.asarray(m, np.float32).reshape(3, 3)
@@ -273,18 +303,24 @@ class YCbCr:
         self.siting = int(siting)
 
     @classmethod
-    def _standard(cls, fill, full_range, siting):
+    def _standard(cls, standard, full_range, siting, bits):
         y = fsr1_ycbcr()
-        _lib.check(getattr(_lib.load(), fill)(ctypes.byref(y), int(bool(full_range))))
+        if _lib.load().fsr1_ycbcr_fill(ctypes.byref(y), standard, int(bool(full_range)), int(bits)):
+            raise Fsr1Error("fsr1_ycbcr_fill: unknown standard %d or depth %s (8, 10, 12 or 16 bits)" % (standard, bits))
         return cls([list(r) for r in y.m], list(y.bias), siting)
 
     @classmethod
-    def bt601(cls, full_range=False, siting=CHROMA_LEFT):
-        return cls._standard("fsr1_ycbcr_bt601", full_range, siting)
+    def bt601(cls, full_range=False, siting=CHROMA_LEFT, bits=8):
+        return cls._standard(YCBCR_BT601, full_range, siting, bits)
 
     @classmethod
-    def bt709(cls, full_range=False, siting=CHROMA_LEFT):
-        return cls._standard("fsr1_ycbcr_bt709", full_range, siting)
+    def bt709(cls, full_range=False, siting=CHROMA_LEFT, bits=8):
+        return cls._standard(YCBCR_BT709, full_range, siting, bits)
+
+    @classmethod
+    def bt2020(cls, full_range=False, siting=CHROMA_LEFT, bits=8):
+        """BT.2020 non-constant luminance: HDR10 with bits=10."""
+        return cls._standard(YCBCR_BT2020, full_range, siting, bits)
 
     def c_struct(self, chroma_offset_bytes=0):
         y = fsr1_ycbcr()
@@ -297,9 +333,9 @@ class YCbCr:
 
 
 class RgbToYCbCr:
-    """fsr1_rgb2ycbcr: the matrix (RGB in {0 to 1} in, codes 0..255 out), bias and chroma siting (CHROMA_CENTER: the 2 x 2 box, or
-    CHROMA_REPLICATE: the top-left pixel) of the NV12 store pinned in include/fsr1_hip.h.  RgbToYCbCr.bt601(full_range=False) /
-    RgbToYCbCr.bt709(...) fill the standard coefficients."""
+    """fsr1_rgb2ycbcr: the matrix (RGB in {0 to 1} in, codes 0..2^bits - 1 out), bias and chroma siting (CHROMA_CENTER: the 2 x 2 box, or
+    CHROMA_REPLICATE: the top-left pixel) of the NV12 / P010 / P016 store pinned in include/fsr1_hip.h.  RgbToYCbCr.bt601(full_range=False) /
+    RgbToYCbCr.bt709(...) / RgbToYCbCr.bt2020(...) fill the standard coefficients for codes of `bits` = 8, 10, 12 or 16 (fsr1_rgb2ycbcr_fill)."""
 
     def __init__(self, m, bias, siting=CHROMA_CENTER):
         self.m = np.asarray(m, np.float32).reshape(3, 3)
@@ -307,18 +343,23 @@ class RgbToYCbCr:
         self.siting = int(siting)
 
     @classmethod
-    def _standard(cls, fill, full_range, siting):
+    def _standard(cls, standard, full_range, siting, bits):
         y = fsr1_rgb2ycbcr()
-        _lib.check(getattr(_lib.load(), fill)(ctypes.byref(y), int(bool(full_range))))
+        if _lib.load().fsr1_rgb2ycbcr_fill(ctypes.byref(y), standard, int(bool(full_range)), int(bits)):
+            raise Fsr1Error("fsr1_rgb2ycbcr_fill: unknown standard %d or depth %s (8, 10, 12 or 16 bits)" % (standard, bits))
         return cls([list(r) for r in y.m], list(y.bias), siting)
 
     @classmethod
-    def bt601(cls, full_range=False, siting=CHROMA_CENTER):
-        return cls._standard("fsr1_rgb2ycbcr_bt601", full_range, siting)
+    def bt601(cls, full_range=False, siting=CHROMA_CENTER, bits=8):
+        return cls._standard(YCBCR_BT601, full_range, siting, bits)
 
     @classmethod
-    def bt709(cls, full_range=False, siting=CHROMA_CENTER):
-        return cls._standard("fsr1_rgb2ycbcr_bt709", full_range, siting)
+    def bt709(cls, full_range=False, siting=CHROMA_CENTER, bits=8):
+        return cls._standard(YCBCR_BT709, full_range, siting, bits)
+
+    @classmethod
+    def bt2020(cls, full_range=False, siting=CHROMA_CENTER, bits=8):
+        return cls._standard(YCBCR_BT2020, full_range, siting, bits)
 
     def c_struct(self, chroma_offset_bytes=0):
         y = fsr1_rgb2ycbcr()
@@ -339,7 +380,7 @@ def image_of(t):
       Mono(float16 / float32 / uint8, shaped (H,W), (N,H,W) or (N,1,H,W))  -> R16F / R32F / R8_UNORM
     Row and frame strides are honoured; the innermost (x[, channel]) dims must be dense."""
     import torch
-    if isinstance(t, (Planar, Rgb, Mono, Nv12)):  # (Nv12: so that the calls that do not take it refuse it in the library's words)
+    if isinstance(t, (Planar, Rgb, Mono, Nv12)):  # (Nv12 and its subclasses P010 / P016: so that the calls that do not take it refuse it in the library's words)
         return t.image()
     if not t.is_cuda:
         raise Fsr1Error("image tensors must live on the GPU (got %s); there is no CPU path" % t.device)

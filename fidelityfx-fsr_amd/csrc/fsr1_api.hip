@@ -54,9 +54,9 @@ size_t easu_mono_lds_bytes(int fp_w, int fp_h);
 hipError_t rcas_mono_launch(const RcasArgs& a, int fmt, bool exact, bool wide, hipStream_t stream);
 void rcas_mono_geometry(int fmt, int width, int height, int frames, bool overlapped, int cus, int* tiles_x, int* tiles_y, int* rows);
 size_t rcas_mono_access_bytes(int fmt);
-hipError_t rcas_nv12_launch(const RcasArgs& a, const fsr1_rgb2ycbcr& yc, long long chroma_offset, int fin, bool exact, bool wide, hipStream_t stream);
-hipError_t easu_nv12_launch(const EasuArgs& a, const fsr1_ycbcr& ycbcr, long long chroma_offset, int fout, bool exact, bool s2, bool wide, hipStream_t stream);
-size_t easu_nv12_lds_bytes(int fp_w, int fp_h);
+hipError_t rcas_nv12_launch(const RcasArgs& a, const fsr1_rgb2ycbcr& yc, long long chroma_offset, int bits, int fin, bool exact, bool wide, hipStream_t stream);
+hipError_t easu_nv12_launch(const EasuArgs& a, const fsr1_ycbcr& ycbcr, long long chroma_offset, int bits, int fout, bool exact, bool s2, bool wide, hipStream_t stream);
+size_t easu_nv12_lds_bytes(int fp_w, int fp_h, int pair_bytes);
 }  // namespace fsr1
 
 using namespace fsr1;
@@ -167,11 +167,19 @@ static size_t pixel_bytes(int fmt) {
 }
 
 // NV12 (fsr1_hip.h) is an input and an output of the *_ycbcr entry points alone: what every other entry point answers
-static int nv12_refusal(const char* name) {
-  return fail(FSR1_ERR_UNSUPPORTED, "%s: NV12 images are served by the fsr1_*_ycbcr entry points only", name);
+// P010 / P016: NV12's arrangement in 16-bit words, under NV12's rules everywhere — each by its own name in the messages.
+static bool is_nv12_like(int fmt) { return fmt == FSR1_FORMAT_NV12 || fmt == FSR1_FORMAT_P010 || fmt == FSR1_FORMAT_P016; }
+static const char* nv12_name(int fmt) { return fmt == FSR1_FORMAT_P010 ? "P010" : (fmt == FSR1_FORMAT_P016 ? "P016" : "NV12"); }
+static int nv12_bits(int fmt) { return fmt == FSR1_FORMAT_P010 ? 10 : (fmt == FSR1_FORMAT_P016 ? 16 : 8); }
+static long long nv12_word_bytes(int fmt) { return fmt == FSR1_FORMAT_NV12 ? 1 : 2; }  // a Y code; a (Cb, Cr) pair is two of them
+static int nv12_refusal(const char* name, int fmt) {
+  return fail(FSR1_ERR_UNSUPPORTED, "%s: %s images are served by the fsr1_*_ycbcr entry points only", name, nv12_name(fmt));
 }
 
-static bool any_nv12(const fsr1_image* a, const fsr1_image* b) { return (a && a->format == FSR1_FORMAT_NV12) || (b && b->format == FSR1_FORMAT_NV12); }
+// the NV12-like format of either image, 0 if neither has one
+static int any_nv12(const fsr1_image* a, const fsr1_image* b) {
+  return a && is_nv12_like(a->format) ? a->format : (b && is_nv12_like(b->format) ? b->format : 0);
+}
 
 static int check_image(const fsr1_image* im, const char* name, ImageView* v) {
   if (!im) return fail(FSR1_ERR_INVALID_ARGUMENT, "%s: null image descriptor", name);
@@ -180,7 +188,7 @@ static int check_image(const fsr1_image* im, const char* name, ImageView* v) {
     return fail(FSR1_ERR_INVALID_ARGUMENT, "%s: bad extent %dx%dx%d", name, im->width, im->height, im->frames);
   if (im->width > (1 << 20) || im->height > (1 << 20))  // pixel coordinates stay exact in binary32 with room to spare
     return fail(FSR1_ERR_UNSUPPORTED, "%s: extent %dx%d beyond 2^20 pixels per side", name, im->width, im->height);
-  if (im->format == FSR1_FORMAT_NV12) return nv12_refusal(name);
+  if (is_nv12_like(im->format)) return nv12_refusal(name, im->format);
   if (!format_known(im->format))
     return fail(FSR1_ERR_UNSUPPORTED, "%s: unsupported format %d", name, im->format);
   const size_t px = pixel_bytes(im->format);
@@ -426,7 +434,7 @@ int fsr1_easu_dispatch_band(const fsr1_image* in, const fsr1_image* out, const u
   if (origin_x < 0 || origin_y < 0 || origin_x > (1 << 20) || origin_y > (1 << 20))
     return fail(FSR1_ERR_INVALID_ARGUMENT, "easu band: origin (%d, %d) out of range", origin_x, origin_y);
   if (flags & FSR1_FLAG_MATH_PACKED_FP16) return fail(FSR1_ERR_UNSUPPORTED, "easu band: bands run with the F (binary32) arithmetic");
-  if (any_nv12(in, out)) return nv12_refusal("easu band");
+  if (const int f = any_nv12(in, out)) return nv12_refusal("easu band", f);
   if (any_mono(in, out)) return fail(FSR1_ERR_UNSUPPORTED, "easu band: row bands are not built for single-channel images");
   if (any_rgb3(in, out)) return fail(FSR1_ERR_UNSUPPORTED, "easu band: row bands are not built for 3-channel images");
   if (any_planar(in, out)) return fail(FSR1_ERR_UNSUPPORTED, "easu band: row bands are not built for planar images");
@@ -641,7 +649,7 @@ int fsr1_rcas_dispatch_band(const fsr1_image* in, const fsr1_image* out, const u
                             int32_t rows_below, void* stream) {
   if ((rows_above | rows_below) & ~1) return fail(FSR1_ERR_INVALID_ARGUMENT, "rcas band: rows_above / rows_below must be 0 or 1");
   if (flags & FSR1_FLAG_MATH_PACKED_FP16) return fail(FSR1_ERR_UNSUPPORTED, "rcas band: bands run with the F (binary32) arithmetic");
-  if (any_nv12(in, out)) return nv12_refusal("rcas band");
+  if (const int f = any_nv12(in, out)) return nv12_refusal("rcas band", f);
   if (any_mono(in, out)) return fail(FSR1_ERR_UNSUPPORTED, "rcas band: row bands are not built for single-channel images");
   if (any_rgb3(in, out)) return fail(FSR1_ERR_UNSUPPORTED, "rcas band: row bands are not built for 3-channel images");
   if (any_planar(in, out)) return fail(FSR1_ERR_UNSUPPORTED, "rcas band: row bands are not built for planar images");
@@ -912,7 +920,7 @@ static int upscale_decide(const char* who, const fsr1_image* in, bool have_inter
   for (const fsr1_image* im : {in, out}) {
     if (im->width <= 0 || im->height <= 0 || im->frames <= 0)
       return fail(FSR1_ERR_INVALID_ARGUMENT, "%s: bad %s extent %dx%dx%d", who, im == in ? "input" : "output", im->width, im->height, im->frames);
-    if (im->format == FSR1_FORMAT_NV12) return nv12_refusal(who);
+    if (is_nv12_like(im->format)) return nv12_refusal(who, im->format);
     if (!format_known(im->format))
       return fail(FSR1_ERR_UNSUPPORTED, "%s: unsupported %s format %d", who, im == in ? "input" : "output", im->format);
   }
@@ -1035,30 +1043,35 @@ int fsr1_upscale_plan(const fsr1_image* in, int32_t have_intermediary, const fsr
 
 // ---- NV12 in, planar RGB out (include/fsr1_hip.h, fsr1_easu_nv12.hip) ----
 // An NV12 descriptor and its fsr1_ycbcr -> the view of the Y plane (whose pitch and frame stride the chroma plane shares), the resolved
-// chroma offset and the bytes of one frame.  check_image's rules with the element being a Cb, Cr pair: multiples of 2 everywhere.
+// chroma offset and the bytes of one frame.  check_image's rules with the element being a Cb, Cr pair: multiples of 2 everywhere — of 4
+// for P010 / P016, whose pairs of 16-bit words are aligned dwords.
 // conv / conv_name: the caller's fsr1_ycbcr (an input) or fsr1_rgb2ycbcr (an output), of which siting_ok, siting and offset are its words.
 static int check_nv12(const fsr1_image* im, const void* conv, const char* conv_name, bool siting_ok, int siting, long long offset, const char* name,
                       const char* role, ImageView* v, long long* chroma_offset, long long* frame_bytes) {
   if (!im) return fail(FSR1_ERR_INVALID_ARGUMENT, "%s: null image descriptor", name);
-  if (im->format != FSR1_FORMAT_NV12) return fail(FSR1_ERR_UNSUPPORTED, "%s: the %s must be FSR1_FORMAT_NV12, got format %d", name, role, im->format);
+  if (!is_nv12_like(im->format)) return fail(FSR1_ERR_UNSUPPORTED, "%s: the %s must be FSR1_FORMAT_NV12, P010 or P016, got format %d", name, role, im->format);
+  const char* const fmt = nv12_name(im->format);
+  const long long pb = 2 * nv12_word_bytes(im->format);  // bytes of a pair: what everything is a multiple of
   if (!conv) return fail(FSR1_ERR_INVALID_ARGUMENT, "%s: null %s", name, conv_name);
   if (!im->data) return fail(FSR1_ERR_INVALID_ARGUMENT, "%s: null data pointer", name);
   if (im->width <= 0 || im->height <= 0 || im->frames <= 0)
     return fail(FSR1_ERR_INVALID_ARGUMENT, "%s: bad extent %dx%dx%d", name, im->width, im->height, im->frames);
   if (im->width > (1 << 20) || im->height > (1 << 20))
     return fail(FSR1_ERR_UNSUPPORTED, "%s: extent %dx%d beyond 2^20 pixels per side", name, im->width, im->height);
-  if (!siting_ok) return fail(FSR1_ERR_UNSUPPORTED, "%s: %s NV12 chroma siting %d", name, siting == FSR1_CHROMA_LEFT ? "unsupported" : "unknown", siting);
+  if (!siting_ok) return fail(FSR1_ERR_UNSUPPORTED, "%s: %s %s chroma siting %d", name, siting == FSR1_CHROMA_LEFT ? "unsupported" : "unknown", fmt, siting);
   const long long cw = (im->width + 1) / 2, ch = (im->height + 1) / 2;
-  const long long pitch = im->row_pitch_bytes ? im->row_pitch_bytes : 2 * cw;
-  if (pitch < 2 * cw || pitch % 2)
-    return fail(FSR1_ERR_INVALID_ARGUMENT, "%s: NV12 row pitch %lld must be even and hold %lld bytes of chroma pairs", name, pitch, 2 * cw);
+  const long long pitch = im->row_pitch_bytes ? im->row_pitch_bytes : pb * cw;
+  if (pitch < pb * cw || pitch % pb)
+    return fail(FSR1_ERR_INVALID_ARGUMENT, "%s: %s row pitch %lld must be a multiple of %lld and hold %lld bytes of chroma pairs", name, fmt, pitch, pb, pb * cw);
   const long long coff = offset ? offset : pitch * im->height;
-  if (coff < pitch * im->height || coff % 2 || coff > (1ll << 40))
-    return fail(FSR1_ERR_INVALID_ARGUMENT, "%s: NV12 chroma offset %lld must be even and at least pitch x height = %lld", name, coff, pitch * im->height);
+  if (coff < pitch * im->height || coff % pb || coff > (1ll << 40))
+    return fail(FSR1_ERR_INVALID_ARGUMENT, "%s: %s chroma offset %lld must be a multiple of %lld and at least pitch x height = %lld", name, fmt, coff, pb,
+                pitch * im->height);
   const long long fbytes = coff + pitch * ch;
   const long long fstride = im->frame_stride_bytes ? im->frame_stride_bytes : fbytes;
-  if (im->frames > 1 && fstride < fbytes) return fail(FSR1_ERR_INVALID_ARGUMENT, "%s: frame stride %lld smaller than one NV12 frame", name, fstride);
-  if (((uintptr_t)im->data % 2) || (fstride % 2)) return fail(FSR1_ERR_INVALID_ARGUMENT, "%s: NV12 data pointer / frame stride must be even", name);
+  if (im->frames > 1 && fstride < fbytes) return fail(FSR1_ERR_INVALID_ARGUMENT, "%s: frame stride %lld smaller than one %s frame", name, fstride, fmt);
+  if (((uintptr_t)im->data % pb) || (fstride % pb))
+    return fail(FSR1_ERR_INVALID_ARGUMENT, "%s: %s data pointer / frame stride must be multiples of %lld", name, fmt, pb);
   v->base = static_cast<char*>(im->data);
   v->width = im->width;
   v->height = im->height;
@@ -1069,7 +1082,9 @@ static int check_nv12(const fsr1_image* im, const void* conv, const char* conv_n
   return FSR1_OK;
 }
 
-static size_t nv12_footprint_lds_bytes(int, int fp_w, int fp_h) { return easu_nv12_lds_bytes(fp_w, fp_h); }  // records + the chroma pairs
+static size_t nv12_footprint_lds_bytes(int fmt, int fp_w, int fp_h) {  // records + the chroma pairs of the input's word width
+  return easu_nv12_lds_bytes(fp_w, fp_h, (int)(2 * nv12_word_bytes(fmt)));
+}
 
 int fsr1_easu_dispatch_ycbcr(const fsr1_image* in, const fsr1_image* out, const uint32_t con[16], const fsr1_ycbcr* ycbcr, uint32_t flags,
                              void* stream) {
@@ -1083,11 +1098,14 @@ int fsr1_easu_dispatch_ycbcr(const fsr1_image* in, const fsr1_image* out, const 
   if (int rc = check_nv12(in, ycbcr, "fsr1_ycbcr", siting_ok, ycbcr ? ycbcr->siting : 0, ycbcr ? ycbcr->chroma_offset_bytes : 0, "easu_ycbcr input", "input",
                           &a.in, &chroma_offset, &frame_bytes))
     return rc;
-  if (out && out->format == FSR1_FORMAT_NV12) return fail(FSR1_ERR_UNSUPPORTED, "easu_ycbcr output: there is no EASU with an NV12 store (fsr1_rcas_dispatch_ycbcr has one)");
+  if (out && is_nv12_like(out->format))
+    return fail(FSR1_ERR_UNSUPPORTED, "easu_ycbcr output: there is no EASU with an %s store (fsr1_rcas_dispatch_ycbcr has one)", nv12_name(out->format));
   if (int rc = check_image(out, "easu_ycbcr output", &a.out)) return rc;
   if (!is_planar(out->format))
-    return fail(FSR1_ERR_UNSUPPORTED, "easu_ycbcr: an NV12 input needs a planar output (RGB16F_PLANAR, RGB32F_PLANAR or RGB8_UNORM_PLANAR), got format %d", out->format);
-  if (flags & FSR1_FLAG_MATH_PACKED_FP16) return fail(FSR1_ERR_UNSUPPORTED, "easu_ycbcr: NV12 images run with the F (binary32) arithmetic, not packed fp16");
+    return fail(FSR1_ERR_UNSUPPORTED, "easu_ycbcr: an %s input needs a planar output (RGB16F_PLANAR, RGB32F_PLANAR or RGB8_UNORM_PLANAR), got format %d",
+                nv12_name(in->format), out->format);
+  if (flags & FSR1_FLAG_MATH_PACKED_FP16)
+    return fail(FSR1_ERR_UNSUPPORTED, "easu_ycbcr: %s images run with the F (binary32) arithmetic, not packed fp16", nv12_name(in->format));
   if (!con) return fail(FSR1_ERR_INVALID_ARGUMENT, "easu_ycbcr: null constants");
   if (in->frames != out->frames) return fail(FSR1_ERR_INVALID_ARGUMENT, "easu_ycbcr: frame counts differ (%d vs %d)", in->frames, out->frames);
   {  // the overlap test of the other dispatches, over what an NV12 batch occupies: its last frame ends behind its chroma plane
@@ -1101,7 +1119,7 @@ int fsr1_easu_dispatch_ycbcr(const fsr1_image* in, const fsr1_image* out, const 
   bool s2 = false;
   if (int rc = easu_planar_geometry(out, a, con, flags, nv12_footprint_lds_bytes, in->format, &s2)) return rc;
   const bool wide = planar_aligned(out, a.out, out->format == FSR1_FORMAT_RGB8_UNORM_PLANAR ? 4 : 2 * pixel_bytes(out->format));
-  if (const hipError_t e = easu_nv12_launch(a, *ycbcr, chroma_offset, out->format, exact, s2, wide, static_cast<hipStream_t>(stream)); e != hipSuccess)
+  if (const hipError_t e = easu_nv12_launch(a, *ycbcr, chroma_offset, nv12_bits(in->format), out->format, exact, s2, wide, static_cast<hipStream_t>(stream)); e != hipSuccess)
     return hip_fail(e, "easu_ycbcr launch");
   return FSR1_OK;
 }
@@ -1111,9 +1129,10 @@ int fsr1_upscale_ycbcr(const fsr1_image* in, const fsr1_image* intermediary, con
                        const fsr1_ycbcr* ycbcr, void* stream) {
   const Range range("upscale_ycbcr", in, out);
   if (!in || !out || !p) return fail(FSR1_ERR_INVALID_ARGUMENT, "upscale_ycbcr: null argument");
-  if (in->format != FSR1_FORMAT_NV12) return fail(FSR1_ERR_UNSUPPORTED, "upscale_ycbcr: the input must be FSR1_FORMAT_NV12, got format %d", in->format);
+  if (!is_nv12_like(in->format)) return fail(FSR1_ERR_UNSUPPORTED, "upscale_ycbcr: needs an NV12, P010 or P016 input, got format %d", in->format);
+  const char* const fmt = nv12_name(in->format);
   if (!is_planar(out->format) || (p->use_rcas && intermediary && intermediary->format != out->format))  // (before anything is launched)
-    return fail(FSR1_ERR_UNSUPPORTED, "upscale_ycbcr: an NV12 input needs a planar output and an intermediary of the same planar format");
+    return fail(FSR1_ERR_UNSUPPORTED, "upscale_ycbcr: an %s input needs a planar output and an intermediary of the same planar format", fmt);
   if (int rc = check_flags(p->flags)) return rc;
   const uint32_t math = p->flags & (FSR1_FLAG_MATH_EXACT | FSR1_FLAG_MATH_PACKED_FP16 | FSR1_FLAG_MATH_STRICT | FSR1_FLAG_NO_FAST_PATHS | FSR1_FLAG_FRAMES_OVERLAP);
   const uint32_t rcas_opts = p->flags & FSR1_FLAG_RCAS_DENOISE;
@@ -1122,7 +1141,7 @@ int fsr1_upscale_ycbcr(const fsr1_image* in, const fsr1_image* intermediary, con
     return fail(FSR1_ERR_INVALID_ARGUMENT, "upscale_ycbcr: params.flags may only hold MATH_*, RCAS_DENOISE, OUTPUT_* and FRAMES_OVERLAP bits");
   if (p->use_rcas && p->fused != 0 && p->fused != 1 && p->fused != 2) return fail(FSR1_ERR_INVALID_ARGUMENT, "upscale_ycbcr: params.fused must be 0, 1 or 2 (auto)");
   if (p->use_rcas && (p->fused == 1 || !intermediary))
-    return fail(FSR1_ERR_UNSUPPORTED, "upscale_ycbcr: NV12 images run as two dispatches; pass an intermediary and fused = 0 or 2");
+    return fail(FSR1_ERR_UNSUPPORTED, "upscale_ycbcr: %s images run as two dispatches; pass an intermediary and fused = 0 or 2", fmt);
   if (in->width <= 0 || in->height <= 0 || out->width <= 0 || out->height <= 0)
     return fail(FSR1_ERR_INVALID_ARGUMENT, "upscale_ycbcr: bad extent %dx%d -> %dx%d", in->width, in->height, out->width, out->height);
   if (!(p->render_width >= 1.0f) || !(p->render_height >= 1.0f) || p->render_width > (float)in->width || p->render_height > (float)in->height)
@@ -1148,14 +1167,17 @@ int fsr1_rcas_dispatch_ycbcr(const fsr1_image* in, const fsr1_image* out, const 
   long long chroma_offset = 0, frame_bytes = 0;
   if (int rc = check_flags(flags)) return rc;
   if (in && !is_planar(in->format))
-    return fail(FSR1_ERR_UNSUPPORTED, "rcas_ycbcr: an NV12 output needs a planar input (RGB16F_PLANAR, RGB32F_PLANAR or RGB8_UNORM_PLANAR), got format %d", in->format);
+    return fail(FSR1_ERR_UNSUPPORTED, "rcas_ycbcr: an %s output needs a planar input (RGB16F_PLANAR, RGB32F_PLANAR or RGB8_UNORM_PLANAR), got format %d",
+                out && is_nv12_like(out->format) ? nv12_name(out->format) : "NV12, P010 or P016", in->format);
   if (int rc = check_image(in, "rcas_ycbcr input", &a.in)) return rc;
   const bool siting_ok = yc && (yc->siting == FSR1_CHROMA_REPLICATE || yc->siting == FSR1_CHROMA_CENTER);
   if (int rc = check_nv12(out, yc, "fsr1_rgb2ycbcr", siting_ok, yc ? yc->siting : 0, yc ? yc->chroma_offset_bytes : 0, "rcas_ycbcr output", "output", &a.out,
                           &chroma_offset, &frame_bytes))
     return rc;
-  if (flags & FSR1_FLAG_MATH_PACKED_FP16) return fail(FSR1_ERR_UNSUPPORTED, "rcas_ycbcr: NV12 images run with the F (binary32) arithmetic, not packed fp16");
-  if (flags & FSR1_FLAG_RCAS_PASSTHROUGH_ALPHA) return fail(FSR1_ERR_UNSUPPORTED, "rcas_ycbcr: planar and NV12 images have no alpha to pass through");
+  if (flags & FSR1_FLAG_MATH_PACKED_FP16)
+    return fail(FSR1_ERR_UNSUPPORTED, "rcas_ycbcr: %s images run with the F (binary32) arithmetic, not packed fp16", nv12_name(out->format));
+  if (flags & FSR1_FLAG_RCAS_PASSTHROUGH_ALPHA)
+    return fail(FSR1_ERR_UNSUPPORTED, "rcas_ycbcr: planar and %s images have no alpha to pass through", nv12_name(out->format));
   if (!con) return fail(FSR1_ERR_INVALID_ARGUMENT, "rcas_ycbcr: null constants");
   if (in->width != out->width || in->height != out->height || in->frames != out->frames)
     return fail(FSR1_ERR_INVALID_ARGUMENT, "rcas_ycbcr: input %dx%dx%d and output %dx%dx%d extents differ", in->width, in->height, in->frames, out->width,
@@ -1173,11 +1195,12 @@ int fsr1_rcas_dispatch_ycbcr(const fsr1_image* in, const fsr1_image* out, const 
   if (int rc = check_grid("rcas_ycbcr", a.tiles_x, a.tiles_y, a.frames)) return rc;
   a.flags = resolve_output_policy(flags, true);
   a.rows_above = a.rows_below = 0;
-  // the input by the planar rule; the surface: dword stores into both planes
-  const bool wide = planar_aligned(in, a.in, 4 * pixel_bytes(in->format)) && (uintptr_t)a.out.base % 4 == 0 && a.out.pitch % 4 == 0 && chroma_offset % 4 == 0 &&
-                    a.out.frame_stride % 4 == 0;
+  // the input by the planar rule; the surface: a lane's four Y codes, or its two pairs, as one store into either plane — 4 bytes (NV12), 8 (P010 / P016)
+  const long long sb = 4 * nv12_word_bytes(out->format);
+  const bool wide = planar_aligned(in, a.in, 4 * pixel_bytes(in->format)) && (uintptr_t)a.out.base % sb == 0 && a.out.pitch % sb == 0 && chroma_offset % sb == 0 &&
+                    a.out.frame_stride % sb == 0;
   const bool exact = (flags & (FSR1_FLAG_MATH_EXACT | FSR1_FLAG_MATH_STRICT)) != 0;
-  if (const hipError_t e = rcas_nv12_launch(a, *yc, chroma_offset, in->format, exact, wide, static_cast<hipStream_t>(stream)); e != hipSuccess)
+  if (const hipError_t e = rcas_nv12_launch(a, *yc, chroma_offset, nv12_bits(out->format), in->format, exact, wide, static_cast<hipStream_t>(stream)); e != hipSuccess)
     return hip_fail(e, "rcas_ycbcr launch");
   return FSR1_OK;
 }
@@ -1187,20 +1210,22 @@ int fsr1_transcode_ycbcr(const fsr1_image* in, const fsr1_image* intermediary, c
                          const fsr1_rgb2ycbcr* ycbcr_out, void* stream) {
   const Range range("transcode_ycbcr", in, out);
   if (!in || !out || !p) return fail(FSR1_ERR_INVALID_ARGUMENT, "transcode_ycbcr: null argument");
-  if (in->format != FSR1_FORMAT_NV12 || out->format != FSR1_FORMAT_NV12)
-    return fail(FSR1_ERR_UNSUPPORTED, "transcode_ycbcr: input and output must be FSR1_FORMAT_NV12, got formats %d -> %d", in->format, out->format);
+  if (!is_nv12_like(in->format) || !is_nv12_like(out->format))
+    return fail(FSR1_ERR_UNSUPPORTED, "transcode_ycbcr: input and output must each be FSR1_FORMAT_NV12, P010 or P016, got formats %d -> %d", in->format, out->format);
+  const char* const fmt = nv12_name(in->format);
   if (int rc = check_flags(p->flags)) return rc;
   const uint32_t math = p->flags & (FSR1_FLAG_MATH_EXACT | FSR1_FLAG_MATH_PACKED_FP16 | FSR1_FLAG_MATH_STRICT | FSR1_FLAG_NO_FAST_PATHS | FSR1_FLAG_FRAMES_OVERLAP);
   const uint32_t rcas_opts = p->flags & FSR1_FLAG_RCAS_DENOISE;
   const uint32_t out_policy = p->flags & (FSR1_FLAG_OUTPUT_STREAMING | FSR1_FLAG_OUTPUT_CACHED);  // of the pass that writes `out`
   if (p->flags & ~(math | rcas_opts | out_policy))
     return fail(FSR1_ERR_INVALID_ARGUMENT, "transcode_ycbcr: params.flags may only hold MATH_*, RCAS_DENOISE, OUTPUT_* and FRAMES_OVERLAP bits");
-  if (!p->use_rcas) return fail(FSR1_ERR_UNSUPPORTED, "transcode_ycbcr: the NV12 store is RCAS's; there is no EASU with an NV12 output (use_rcas = 0)");
+  if (!p->use_rcas)
+    return fail(FSR1_ERR_UNSUPPORTED, "transcode_ycbcr: the %s store is RCAS's; there is no EASU with such an output (use_rcas = 0)", nv12_name(out->format));
   if (p->fused != 0 && p->fused != 1 && p->fused != 2) return fail(FSR1_ERR_INVALID_ARGUMENT, "transcode_ycbcr: params.fused must be 0, 1 or 2 (auto)");
   if (p->fused == 1 || !intermediary)
-    return fail(FSR1_ERR_UNSUPPORTED, "transcode_ycbcr: NV12 images run as two dispatches; pass an intermediary and fused = 0 or 2");
+    return fail(FSR1_ERR_UNSUPPORTED, "transcode_ycbcr: %s images run as two dispatches; pass an intermediary and fused = 0 or 2", fmt);
   if (!is_planar(intermediary->format))
-    return fail(FSR1_ERR_UNSUPPORTED, "transcode_ycbcr: between the NV12 images the intermediary must be planar, got format %d", intermediary->format);
+    return fail(FSR1_ERR_UNSUPPORTED, "transcode_ycbcr: between the %s images the intermediary must be planar, got format %d", fmt, intermediary->format);
   if (in->width <= 0 || in->height <= 0 || out->width <= 0 || out->height <= 0)
     return fail(FSR1_ERR_INVALID_ARGUMENT, "transcode_ycbcr: bad extent %dx%d -> %dx%d", in->width, in->height, out->width, out->height);
   if (!(p->render_width >= 1.0f) || !(p->render_height >= 1.0f) || p->render_width > (float)in->width || p->render_height > (float)in->height)

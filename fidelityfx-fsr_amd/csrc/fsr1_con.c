@@ -89,42 +89,74 @@ void FsrRcasCon(uint32_t* con, float sharpness) {
  *   R = E'y + 2 (1 - Kr) E'pr,  G = E'y - 2 Kb (1 - Kb) / Kg E'pb - 2 Kr (1 - Kr) / Kg E'pr,  B = E'y + 2 (1 - Kb) E'pb
  * (y0, ys, cs) = (16, 219, 224) for limited ("video") range, (0, 255, 255) for full range.  Every coefficient is formed in double and
  * rounded to float once. */
-static int ycbcr_fill(fsr1_ycbcr* y, double kr, double kb, int full_range) {
-  if (!y) return FSR1_ERR_INVALID_ARGUMENT;
+/* The levels of a depth: limited range is the 8-bit levels times 2^(bits - 8) (exact in double), full range 0 .. 2^bits - 1 with the
+ * chroma zero at 2^(bits - 1).  0 for a depth that is not 8, 10, 12 or 16. */
+typedef struct { double y0, ys, cs, c0; } levels;
+static int levels_of(int full_range, int bits, levels* l) {
+  if (bits != 8 && bits != 10 && bits != 12 && bits != 16) return 0;
+  const double up = (double)(1u << (bits - 8)), top = (double)((1u << bits) - 1u);
+  l->y0 = full_range ? 0.0 : 16.0 * up;
+  l->ys = full_range ? top : 219.0 * up;
+  l->cs = full_range ? top : 224.0 * up;
+  l->c0 = 128.0 * up;
+  return 1;
+}
+static int luma_weights(int standard, double* kr, double* kb) {
+  static const double k[3][2] = {{0.299, 0.114}, {0.2126, 0.0722}, {0.2627, 0.0593}};  /* BT.601, BT.709, BT.2020 (non-constant luminance) */
+  if (standard < FSR1_YCBCR_BT601 || standard > FSR1_YCBCR_BT2020) return 0;
+  *kr = k[standard][0];
+  *kb = k[standard][1];
+  return 1;
+}
+
+static int ycbcr_fill(fsr1_ycbcr* y, double kr, double kb, int full_range, int bits) {
+  levels l;
+  if (!y || !levels_of(full_range, bits, &l)) return FSR1_ERR_INVALID_ARGUMENT;
   const double kg = 1.0 - kr - kb;
-  const double y0 = full_range ? 0.0 : 16.0, ys = full_range ? 255.0 : 219.0, cs = full_range ? 255.0 : 224.0;
+  const double y0 = l.y0, ys = l.ys, cs = l.cs;
   const double m[3][3] = {{1.0 / ys, 0.0, 2.0 * (1.0 - kr) / cs},
                           {1.0 / ys, -2.0 * kb * (1.0 - kb) / kg / cs, -2.0 * kr * (1.0 - kr) / kg / cs},
                           {1.0 / ys, 2.0 * (1.0 - kb) / cs, 0.0}};
   for (int r = 0; r < 3; ++r) {
     for (int c = 0; c < 3; ++c) y->m[r][c] = (float)m[r][c];
-    y->bias[r] = (float)(-(y0 * m[r][0] + 128.0 * (m[r][1] + m[r][2])));
+    y->bias[r] = (float)(-(y0 * m[r][0] + l.c0 * (m[r][1] + m[r][2])));
   }
   y->siting = FSR1_CHROMA_LEFT;
   y->chroma_offset_bytes = 0;
   return FSR1_OK;
 }
 
-int fsr1_ycbcr_bt601(fsr1_ycbcr* ycbcr, int full_range) { return ycbcr_fill(ycbcr, 0.299, 0.114, full_range); }
-int fsr1_ycbcr_bt709(fsr1_ycbcr* ycbcr, int full_range) { return ycbcr_fill(ycbcr, 0.2126, 0.0722, full_range); }
+int fsr1_ycbcr_bt601(fsr1_ycbcr* ycbcr, int full_range) { return ycbcr_fill(ycbcr, 0.299, 0.114, full_range, 8); }
+int fsr1_ycbcr_bt709(fsr1_ycbcr* ycbcr, int full_range) { return ycbcr_fill(ycbcr, 0.2126, 0.0722, full_range, 8); }
+int fsr1_ycbcr_fill(fsr1_ycbcr* ycbcr, int standard, int full_range, int bits) {
+  double kr, kb;
+  if (!luma_weights(standard, &kr, &kb)) return FSR1_ERR_INVALID_ARGUMENT;
+  return ycbcr_fill(ycbcr, kr, kb, full_range, bits);
+}
 
 /* RGB -> YCbCr matrices for RGB in {0 to 1} in, codes 0 .. 255 out (fsr1_rgb2ycbcr, include/fsr1_hip.h), from the same Kr, Kb:
  *   Y = y0 + ys (Kr R + Kg G + Kb B),  Cb = 128 + cs (B - E'y) / (2 (1 - Kb)),  Cr = 128 + cs (R - E'y) / (2 (1 - Kr))
  * with E'y = Kr R + Kg G + Kb B.  Every coefficient is formed in double and rounded to float once. */
-static int rgb2ycbcr_fill(fsr1_rgb2ycbcr* y, double kr, double kb, int full_range) {
-  if (!y) return FSR1_ERR_INVALID_ARGUMENT;
+static int rgb2ycbcr_fill(fsr1_rgb2ycbcr* y, double kr, double kb, int full_range, int bits) {
+  levels l;
+  if (!y || !levels_of(full_range, bits, &l)) return FSR1_ERR_INVALID_ARGUMENT;
   const double kg = 1.0 - kr - kb;
-  const double y0 = full_range ? 0.0 : 16.0, ys = full_range ? 255.0 : 219.0, cs = full_range ? 255.0 : 224.0;
+  const double y0 = l.y0, ys = l.ys, cs = l.cs;
   const double cb = cs / (2.0 * (1.0 - kb)), cr = cs / (2.0 * (1.0 - kr));
   const double m[3][3] = {{ys * kr, ys * kg, ys * kb}, {-cb * kr, -cb * kg, cb * (1.0 - kb)}, {cr * (1.0 - kr), -cr * kg, -cr * kb}};
   for (int r = 0; r < 3; ++r) {
     for (int c = 0; c < 3; ++c) y->m[r][c] = (float)m[r][c];
-    y->bias[r] = (float)(r ? 128.0 : y0);
+    y->bias[r] = (float)(r ? l.c0 : y0);
   }
   y->siting = FSR1_CHROMA_CENTER;
   y->chroma_offset_bytes = 0;
   return FSR1_OK;
 }
 
-int fsr1_rgb2ycbcr_bt601(fsr1_rgb2ycbcr* ycbcr, int full_range) { return rgb2ycbcr_fill(ycbcr, 0.299, 0.114, full_range); }
-int fsr1_rgb2ycbcr_bt709(fsr1_rgb2ycbcr* ycbcr, int full_range) { return rgb2ycbcr_fill(ycbcr, 0.2126, 0.0722, full_range); }
+int fsr1_rgb2ycbcr_bt601(fsr1_rgb2ycbcr* ycbcr, int full_range) { return rgb2ycbcr_fill(ycbcr, 0.299, 0.114, full_range, 8); }
+int fsr1_rgb2ycbcr_bt709(fsr1_rgb2ycbcr* ycbcr, int full_range) { return rgb2ycbcr_fill(ycbcr, 0.2126, 0.0722, full_range, 8); }
+int fsr1_rgb2ycbcr_fill(fsr1_rgb2ycbcr* ycbcr, int standard, int full_range, int bits) {
+  double kr, kb;
+  if (!luma_weights(standard, &kr, &kb)) return FSR1_ERR_INVALID_ARGUMENT;
+  return rgb2ycbcr_fill(ycbcr, kr, kb, full_range, bits);
+}

@@ -7,21 +7,26 @@
 // stores is the one the planar kernel of the output's format stores for the converted frame, bit for bit.  What is this file's is
 // phase 1 (include/fsr1_device_nv12.hpp): the tile's chroma pairs go through a small LDS region of their own behind the records
 // (320 bytes at exactly 2x), each lane loads one Y byte per texel, and the output format is free of the input's.
+//
+// FSR1_FORMAT_P010 / P016 (the same arrangement in 16-bit words) are the same kernel with WORD = uint16_t: 32-bit pairs in LDS (640
+// bytes at exactly 2x), one Y word per texel, the depth a run-time shift — 36 more instantiations for both depths together.
 #include "fsr1_device.h"
 #include "fsr1_device_nv12.hpp"
 
 namespace fsr1 {
 
-size_t easu_nv12_lds_bytes(int fp_w, int fp_h) { return easu_lds_region_bytes((size_t)fp_w * fp_h) + nv12_chroma_lds_bytes(fp_w, fp_h); }
+// pair_bytes: 2 (NV12) or 4 (P010 / P016)
+size_t easu_nv12_lds_bytes(int fp_w, int fp_h, int pair_bytes) { return easu_lds_region_bytes((size_t)fp_w * fp_h) + nv12_chroma_lds_bytes(fp_w, fp_h, pair_bytes); }
 
-template <int FOUT, bool EXACT, bool S2, bool HDR, bool WIDE>
+template <int FOUT, bool EXACT, bool S2, bool HDR, bool WIDE, class WORD>
 __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(7, 8))) easu_nv12_kernel(const EasuArgs a, const Nv12View yc) {
   typedef typename Plane<FOUT>::E elem_t;
   constexpr int kS2W = kTileW / 2 + 3, kS2H = kTileH / 2 + 3;  // footprint of every exact-2x tile
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int capacity = S2 ? kS2W * kS2H : a.fp_w * a.fp_h;
   EasuLds l = easu_lds_carve(smem, capacity);
-  uint16_t* const pairs = reinterpret_cast<uint16_t*>(smem + easu_lds_region_bytes((size_t)capacity));
+  typedef typename Nv12Pair<WORD>::T pair_t;
+  pair_t* const pairs = reinterpret_cast<pair_t*>(smem + easu_lds_region_bytes((size_t)capacity));
 
   const int tiles_per_frame = a.tiles_x * a.tiles_y;
   const int t = xcd_swizzle(blockIdx.x, tiles_per_frame * a.frames, a.xcd_shift);
@@ -41,7 +46,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(7
     // the shifted tiles and 2 x 2 quads of the exact-2x variant: fsr1_easu_planar.hip, fsr1_easu_kernel.h
     const int ox0 = tx * kTileW - 1, oy0 = ty * kTileH - 1;
     l.fw = kS2W;
-    easu_stage_footprint_nv12<EXACT, kS2W, kS2H>(l, pairs, a.in, yc, in_frame, tx * (kTileW / 2) - 2, ty * (kTileH / 2) - 2, kS2W, kS2H, tid);
+    easu_stage_footprint_nv12<EXACT, kS2W, kS2H, kThreads, WORD>(l, pairs, a.in, yc, in_frame, tx * (kTileW / 2) - 2, ty * (kTileH / 2) - 2, kS2W, kS2H, tid);
     const int qx = lane & 31, qy = 2 * wave + (lane >> 5);
     const int oxa = ox0 + 2 * qx, oya = oy0 + 2 * qy;
     const bool xin0 = oxa >= 0 && oxa < W, xin1 = oxa + 1 < W, xin2 = oxa + 2 < W, yin0 = oya >= 0 && oya < H, yin1 = oya + 1 < H;
@@ -82,7 +87,7 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(7
   const int fw = min((int)floorf((float)oxl * c0x + c0z) + 2 - fx0 + 1, a.fp_w);
   const int fh = min((int)floorf((float)oyl * c0y + c0w) + 2 - fy0 + 1, a.fp_h);
   l.fw = fw;
-  easu_stage_footprint_nv12<EXACT>(l, pairs, a.in, yc, in_frame, fx0, fy0, fw, fh, tid);
+  easu_stage_footprint_nv12<EXACT, 0, 0, kThreads, WORD>(l, pairs, a.in, yc, in_frame, fx0, fy0, fw, fh, tid);
 
   const int ox = ox0 + easu_lane_column(lane);
   if (ox >= W) return;
@@ -106,19 +111,28 @@ __global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(7
   }
 }
 
+template <int FOUT, bool EXACT, bool S2, bool HDR, bool WIDE, class WORD>
+static hipError_t easu_nv12_launch_word(const EasuArgs& a, const Nv12View& yc, hipStream_t stream) {
+  const dim3 grid((unsigned)(a.tiles_x * a.tiles_y * a.frames)), block(kThreads);
+  const size_t lds = easu_nv12_lds_bytes(a.fp_w, a.fp_h, (int)sizeof(typename Nv12Pair<WORD>::T));
+  if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(&easu_nv12_kernel<FOUT, EXACT, S2, HDR, WIDE, WORD>), lds); e != hipSuccess) return e;
+  hipLaunchKernelGGL((easu_nv12_kernel<FOUT, EXACT, S2, HDR, WIDE, WORD>), grid, block, lds, stream, a, yc);
+  return hipGetLastError();
+}
+
+// the word width by the input's format: yc.shift < 0 marks NV12's bytes
 template <int FOUT, bool EXACT, bool S2, bool HDR, bool WIDE>
 static hipError_t easu_nv12_launch_one(const EasuArgs& a, const Nv12View& yc, hipStream_t stream) {
-  const dim3 grid((unsigned)(a.tiles_x * a.tiles_y * a.frames)), block(kThreads);
-  const size_t lds = easu_nv12_lds_bytes(a.fp_w, a.fp_h);
-  if (hipError_t e = ensure_dynamic_lds(reinterpret_cast<const void*>(&easu_nv12_kernel<FOUT, EXACT, S2, HDR, WIDE>), lds); e != hipSuccess) return e;
-  hipLaunchKernelGGL((easu_nv12_kernel<FOUT, EXACT, S2, HDR, WIDE>), grid, block, lds, stream, a, yc);
-  return hipGetLastError();
+  if (yc.shift < 0) return easu_nv12_launch_word<FOUT, EXACT, S2, HDR, WIDE, uint8_t>(a, yc, stream);
+  return easu_nv12_launch_word<FOUT, EXACT, S2, HDR, WIDE, uint16_t>(a, yc, stream);
 }
 
 // fout: the planar format of the output; s2 / wide as for easu_planar_launch (the host has checked the OUTPUT's base, pitch, plane
 // and frame stride against the wide stores; the input is read one and two bytes at a time whatever its alignment).
 // chroma_offset: bytes from a frame's Y plane to its CbCr plane, resolved and checked by the host.
-hipError_t easu_nv12_launch(const EasuArgs& a, const fsr1_ycbcr& ycbcr, long long chroma_offset, int fout, bool exact, bool s2, bool wide, hipStream_t stream) {
+// bits: 8 = NV12's bytes; 10 / 16 = P010 / P016's words (the host has checked base, pitch, chroma offset and frame stride against the
+// aligned dword a pair then is).
+hipError_t easu_nv12_launch(const EasuArgs& a, const fsr1_ycbcr& ycbcr, long long chroma_offset, int bits, int fout, bool exact, bool s2, bool wide, hipStream_t stream) {
   Nv12View yc;
   for (int r = 0; r < 3; ++r) {
     for (int c = 0; c < 3; ++c) yc.m[r][c] = ycbcr.m[r][c];
@@ -126,6 +140,7 @@ hipError_t easu_nv12_launch(const EasuArgs& a, const fsr1_ycbcr& ycbcr, long lon
   }
   yc.siting = ycbcr.siting;
   yc.chroma_offset = chroma_offset;
+  yc.shift = bits == 8 ? -1 : 16 - bits;
   const bool hdr = (a.flags & FSR1_FLAG_HDR_SQUARE) != 0;
 #define FSR1_NV12_H(F, E, S, V) return hdr ? easu_nv12_launch_one<F, E, S, true, V>(a, yc, stream) : easu_nv12_launch_one<F, E, S, false, V>(a, yc, stream)
 #define FSR1_NV12_E(F)                               \

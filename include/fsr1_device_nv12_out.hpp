@@ -13,6 +13,8 @@ struct Rgb2YcbcrView {
   float bias[3];
   int siting;               // FSR1_CHROMA_CENTER or FSR1_CHROMA_REPLICATE (the host has refused everything else)
   long long chroma_offset;  // bytes from a frame's first Y byte to its first Cb byte
+  float max_code;           // 2^bits - 1: 255 (NV12), 1023 (P010), 65535 (P016)
+  uint32_t shift;           // 16 - bits of a 16-bit format: a stored word is code << shift (P010: the six low bits are zero); NV12: 0
 };
 
 // Row k of the matrix on one RGB value: bias + m0 R, + m1 G, + m2 B with every product and every sum rounded to binary32 by itself.
@@ -24,13 +26,19 @@ __device__ __forceinline__ float nv12_component(const Rgb2YcbcrView& c, int k, r
 }
 
 // The code of a component: the project's UNORM store rule in code units — clamp, one rounded addition of a half, truncation.
-// fmaxf is IEEE maxNum: a NaN becomes 0.
-__device__ __forceinline__ uint32_t nv12_code(float v) {
+// fmaxf is IEEE maxNum: a NaN becomes 0.  max_code, shift: of the format's depth — the result is the word (or byte) the surface holds,
+// code << shift; 65535.5 is a binary32 number, so the rounded addition is what it says at 16 bits too.
+__device__ __forceinline__ uint32_t nv12_code(float v, float max_code = 255.0f, uint32_t shift = 0) {
 #pragma clang fp contract(off)
-  return (uint32_t)__fadd_rn(fminf(fmaxf(v, 0.0f), 255.0f), 0.5f);
+  return (uint32_t)__fadd_rn(fminf(fmaxf(v, 0.0f), max_code), 0.5f) << shift;
 }
 
 __device__ __forceinline__ uint32_t nv12_luma_code(const Rgb2YcbcrView& c, rgb_t p) { return nv12_code(nv12_component(c, 0, p)); }
+// 16-bit words (P010 / P016): the Y word, and the (Cb, Cr) pair as the aligned dword the surface holds, Cb in the low word
+__device__ __forceinline__ uint32_t p016_luma_word(const Rgb2YcbcrView& c, rgb_t p) { return nv12_code(nv12_component(c, 0, p), c.max_code, c.shift); }
+__device__ __forceinline__ uint32_t p016_pair_words(const Rgb2YcbcrView& c, rgb_t a) {
+  return nv12_code(nv12_component(c, 1, a), c.max_code, c.shift) | (nv12_code(nv12_component(c, 2, a), c.max_code, c.shift) << 16);
+}
 
 // The (Cb, Cr) pair of a block from its chroma sample `a`, as the 16 bits the surface holds: Cb in the low byte.
 __device__ __forceinline__ uint32_t nv12_pair_code(const Rgb2YcbcrView& c, rgb_t a) {

@@ -149,7 +149,18 @@ typedef enum fsr1_format {
    *   frame_stride_bytes  0 = chroma offset + pitch * ch
    * Pointer, pitch, chroma offset and frame stride need only be multiples of 2: the kernels read and write Y bytes and 16-bit pairs,
    * nothing wider, unless all four are multiples of 4 (an output then takes dword stores). */
-  FSR1_FORMAT_NV12 = 14               /* 8-bit Y plane + interleaved CbCr plane, 1.5 B/pixel */
+  FSR1_FORMAT_NV12 = 14,              /* 8-bit Y plane + interleaved CbCr plane, 1.5 B/pixel */
+  /* P010 / P016 — NV12's arrangement in 16-bit little-endian words: what every 10-bit (HEVC Main10, AV1, HDR10) decoder writes and
+   * encoder reads.  The CODE of a word is word >> (16 - bits), bits = 10 (P010) or 16 (P016): P010 keeps its code in the upper ten bits,
+   * ignores the low six bits of an input word and stores them as zero.  Everything said of NV12 holds with the bytes doubled: the same
+   * entry points take them as input and as output (any of the three formats on either end of fsr1_transcode_ycbcr), every entry point
+   * that refuses NV12 refuses them the same way with the format's own name ("P010" / "P016") in the message, width / height are the luma
+   * size (odd sizes included), the chroma plane is cw x ch pairs of 4 bytes, row_pitch_bytes 0 = 4 * cw and any other pitch must hold
+   * that many bytes, chroma offset and frame stride follow NV12's rules.  Pointer, pitch, chroma offset and frame stride must be
+   * multiples of 4 — a pair is one aligned dword — anything else is FSR1_ERR_INVALID_ARGUMENT; an output whose four values are all
+   * multiples of 8 takes 8-byte stores (a lane's four Y words, or its two pairs), any other 16-bit Y stores and one dword per pair. */
+  FSR1_FORMAT_P010 = 15,              /* 16-bit words, 10-bit codes in the upper bits, 3 B/pixel */
+  FSR1_FORMAT_P016 = 16               /* 16-bit words, 16-bit codes, 3 B/pixel */
 } fsr1_format;
 
 typedef struct fsr1_image {
@@ -424,6 +435,11 @@ int fsr1_upscale_plan(const fsr1_image* in, int32_t have_intermediary, const fsr
  *     result = min(max(v, 0), 1)
  * A binary32 restatement of these lines (numpy float32) reproduces the staged RGB bit for bit, and the image EASU then stores is the one
  * the planar kernels store for that RGB image in out's format — bit for bit, default arithmetic included.
+ * FSR1_FORMAT_P010 / P016: Y, Cb, Cr are the raw codes 0 .. 2^bits - 1 as binary32 (the code of a word: word >> (16 - bits)); m and
+ * bias map codes of that depth (fsr1_ycbcr_fill).  The reconstruction stays exact in binary32: a 16-bit code, two blends with weights
+ * in quarters and halves — at most 16 + 2 + 2 = 20 significant bits of binary32's 24 — so its order still cannot matter.  The three
+ * rounded conversion steps and the clamp to {0 to 1} are unchanged.  No transfer function is applied: PQ or HLG content is filtered as
+ * encoded.
  * ---------------------------------------------------------------------------------------------- */
 enum { FSR1_CHROMA_REPLICATE = 0, FSR1_CHROMA_LEFT = 1, FSR1_CHROMA_CENTER = 2 };
 
@@ -439,11 +455,19 @@ typedef struct fsr1_ycbcr {
 int fsr1_ycbcr_bt601(fsr1_ycbcr* ycbcr, int full_range);
 int fsr1_ycbcr_bt709(fsr1_ycbcr* ycbcr, int full_range);
 
+/* The same for codes of any depth: standard = FSR1_YCBCR_BT601 / BT709 / BT2020 (BT.2020 non-constant-luminance, Kr 0.2627, Kb 0.0593:
+ * what HDR10 uses), bits = 8, 10, 12 or 16.  Limited range scales the 8-bit levels by 2^(bits - 8) (10 bits: Y 64 .. 940, C 64 .. 960
+ * around 512), full range spans 0 .. 2^bits - 1 with the chroma zero at 2^(bits - 1).  Computed in double, rounded once; bits = 8 gives
+ * the two fillers above bit for bit.  FSR1_ERR_INVALID_ARGUMENT: a null pointer, an unknown standard or depth.  Host, pure. */
+enum { FSR1_YCBCR_BT601 = 0, FSR1_YCBCR_BT709 = 1, FSR1_YCBCR_BT2020 = 2 };
+int fsr1_ycbcr_fill(fsr1_ycbcr* ycbcr, int standard, int full_range, int bits);
+
 /* EASU of an NV12 image into a planar RGB image (FSR1_FORMAT_RGB16F_PLANAR / RGB32F_PLANAR / RGB8_UNORM_PLANAR: the caller picks the
  * output type, the input has none to match).  fsr1_easu_dispatch's validation and overlap test (the chroma plane at its offset
  * included); default F arithmetic or FSR1_FLAG_MATH_EXACT, FSR1_FLAG_MATH_STRICT takes EXACT as for planar; HDR_SQUARE, OUTPUT_* and
  * FRAMES_OVERLAP as for planar.  FSR1_ERR_UNSUPPORTED ("NV12" in the message): an input that is not NV12, an output that is not one
- * of the three planar formats (NV12 included), FSR1_FLAG_MATH_PACKED_FP16, an unknown siting. */
+ * of the three planar formats (NV12 included), FSR1_FLAG_MATH_PACKED_FP16, an unknown siting.  P010 / P016 inputs: the same, by
+ * their own names. */
 int fsr1_easu_dispatch_ycbcr(const fsr1_image* in, const fsr1_image* out, const uint32_t con[16], const fsr1_ycbcr* ycbcr, uint32_t flags,
                              void* stream);
 
@@ -476,6 +500,9 @@ int fsr1_upscale_ycbcr(const fsr1_image* in, const fsr1_image* intermediary, con
  *   No byte outside the width x height Y bytes and the 2 cw x ch pair bytes of a frame is ever written.
  * A binary32 restatement of these lines (numpy float32) on the planar binary32 RCAS result reproduces the surface byte for byte,
  * default arithmetic included.
+ * FSR1_FORMAT_P010 / P016: code = (uint32)(min(max(v, 0), 2^bits - 1) + 0.5f), NaN stores 0, and the stored word is
+ * code << (16 - bits) (65535.5 is a binary32 number, so the rule is what it says for P016 too); m and bias map to raw codes of the
+ * format's depth (fsr1_rgb2ycbcr_fill).  No byte outside the Y words and the pair words of a frame is written.
  * ---------------------------------------------------------------------------------------------- */
 typedef struct fsr1_rgb2ycbcr {
   float m[3][3];               /* rows Y, Cb, Cr; columns R, G, B: RGB in {0 to 1} in, codes 0 .. 255 out */
@@ -488,6 +515,8 @@ typedef struct fsr1_rgb2ycbcr {
  * siting = FSR1_CHROMA_CENTER, chroma_offset_bytes = 0.  Host, pure. */
 int fsr1_rgb2ycbcr_bt601(fsr1_rgb2ycbcr* rgb2ycbcr, int full_range);
 int fsr1_rgb2ycbcr_bt709(fsr1_rgb2ycbcr* rgb2ycbcr, int full_range);
+/* The same for codes of any depth: standard, full_range and bits as for fsr1_ycbcr_fill; bits = 8 gives the two fillers above bit for bit. */
+int fsr1_rgb2ycbcr_fill(fsr1_rgb2ycbcr* rgb2ycbcr, int standard, int full_range, int bits);
 
 /* RCAS of a planar RGB image (any of the three planar formats) into an NV12 image of the same extent.  The planar RCAS dispatch's
  * validation, the NV12 rules above for `out`, the overlap test over what an NV12 batch occupies; default F arithmetic or
@@ -497,7 +526,8 @@ int fsr1_rgb2ycbcr_bt709(fsr1_rgb2ycbcr* rgb2ycbcr, int full_range);
 int fsr1_rcas_dispatch_ycbcr(const fsr1_image* in, const fsr1_image* out, const uint32_t con[4], const fsr1_rgb2ycbcr* rgb2ycbcr,
                              uint32_t flags, void* stream);
 
-/* Decode -> upscale -> encode: NV12 in, fsr1_easu_dispatch_ycbcr into a planar intermediary of any of the three types and out's
+/* Decode -> upscale -> encode: NV12, P010 or P016 in and — independently — out (the two ends are separate dispatches around the planar
+ * intermediary; a uint8 intermediary is legal but quantises a 10-bit transcode to 8 bits), fsr1_easu_dispatch_ycbcr into a planar intermediary of any of the three types and out's
  * extent, fsr1_rcas_dispatch_ycbcr into the NV12 `out`.  fsr1_upscale_ycbcr's parameter rules; use_rcas == 0 (there is no EASU with an
  * NV12 store), fused == 1 and a missing intermediary are FSR1_ERR_UNSUPPORTED ("NV12" in the message). */
 int fsr1_transcode_ycbcr(const fsr1_image* in, const fsr1_image* intermediary, const fsr1_image* out, const fsr1_params* params,
