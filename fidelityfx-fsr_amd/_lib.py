@@ -69,6 +69,16 @@ class fsr1_rgb2ycbcr(ctypes.Structure):
     _fields_ = fsr1_ycbcr._fields_
 
 
+class fsr1_chroma420(ctypes.Structure):
+    """struct fsr1_chroma420 of include/fsr1_hip.h."""
+    _fields_ = [
+        ("siting_in", ctypes.c_int32),
+        ("siting_out", ctypes.c_int32),
+        ("chroma_offset_bytes_in", ctypes.c_int64),
+        ("chroma_offset_bytes_out", ctypes.c_int64),
+    ]
+
+
 _IMG = ctypes.POINTER(fsr1_image)
 _STG = ctypes.POINTER(fsr1_color_stages)
 _YCC = ctypes.POINTER(fsr1_ycbcr)
@@ -103,6 +113,7 @@ SYMBOLS = {
     "fsr1_rgb2ycbcr_fill": (ctypes.c_int, [_R2Y, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "fsr1_rcas_dispatch_ycbcr": (ctypes.c_int, [_IMG, _IMG, _U32P, _R2Y, ctypes.c_uint32, ctypes.c_void_p]),
     "fsr1_transcode_ycbcr": (ctypes.c_int, [_IMG] * 3 + [ctypes.POINTER(fsr1_params), _YCC, _R2Y, ctypes.c_void_p]),
+    "fsr1_transcode_luma": (ctypes.c_int, [_IMG] * 3 + [ctypes.POINTER(fsr1_params), ctypes.POINTER(fsr1_chroma420), ctypes.c_void_p]),
     "fsr1_pipeline_create": (ctypes.c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_int32]),
     "fsr1_pipeline_upscale": (ctypes.c_int, [ctypes.c_void_p, _IMG, _IMG, ctypes.POINTER(fsr1_params), _STG]),
     "fsr1_pipeline_reserve": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t]),

@@ -12,7 +12,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import Fsr1Error, fsr1_color_stages, fsr1_image, fsr1_params, fsr1_rgb2ycbcr, fsr1_ycbcr  # noqa: F401
+from ._lib import Fsr1Error, fsr1_chroma420, fsr1_color_stages, fsr1_image, fsr1_params, fsr1_rgb2ycbcr, fsr1_ycbcr  # noqa: F401
 
 FORMAT_RGBA16F = 0
 FORMAT_RGBA32F = 1
@@ -510,6 +510,21 @@ def transcode_ycbcr(src, mid, dst, ycbcr_in, ycbcr_out, sharpness=0.25, fused=0,
     yo = ycbcr_out.c_struct(dst.chroma_offset_bytes() if isinstance(dst, Nv12) else 0)
     _lib.check(_lib.load().fsr1_transcode_ycbcr(ctypes.byref(i), ctypes.byref(m) if m is not None else None, ctypes.byref(o), ctypes.byref(p),
                                                 ctypes.byref(yi), ctypes.byref(yo), _stream_ptr(stream)))
+    return dst
+
+
+def transcode_luma(src, mid, dst, siting_in=CHROMA_LEFT, siting_out=None, sharpness=0.25, flags=0, stream=None, render_size=None):
+    """Nv12 dst = Upscale(Nv12 src) in the luma domain (fsr1_transcode_luma): EASU + RCAS on the Y plane through `mid` — a Mono uint8
+    tensor of dst's size — and the CbCr plane through a bilinear resampler in RCAS's launch; no RGB, no matrix, no range.
+    siting_in / siting_out: CHROMA_LEFT or CHROMA_CENTER (siting_out=None: as the input)."""
+    i, o = image_of(src), image_of(dst)
+    m = image_of(mid) if mid is not None else None
+    rw, rh = render_size if render_size is not None else (i.width, i.height)
+    p = fsr1_params(float(rw), float(rh), 1, float(sharpness), 0, 0, int(flags))
+    c = fsr1_chroma420(int(siting_in), int(siting_in if siting_out is None else siting_out),
+                       src.chroma_offset_bytes() if isinstance(src, Nv12) else 0, dst.chroma_offset_bytes() if isinstance(dst, Nv12) else 0)
+    _lib.check(_lib.load().fsr1_transcode_luma(ctypes.byref(i), ctypes.byref(m) if m is not None else None, ctypes.byref(o), ctypes.byref(p),
+                                               ctypes.byref(c), _stream_ptr(stream)))
     return dst
 
 

@@ -54,6 +54,9 @@ size_t easu_mono_lds_bytes(int fp_w, int fp_h);
 hipError_t rcas_mono_launch(const RcasArgs& a, int fmt, bool exact, bool wide, hipStream_t stream);
 void rcas_mono_geometry(int fmt, int width, int height, int frames, bool overlapped, int cus, int* tiles_x, int* tiles_y, int* rows);
 size_t rcas_mono_access_bytes(int fmt);
+hipError_t rcas_luma_launch(const RcasArgs& a, const Chroma420Args& c, bool exact, bool wide, bool chroma_only, hipStream_t stream);
+void chroma420_geometry(int CW, int CH, int* tiles_x, int* tiles_y, int* rows);
+int chroma420_run_dwords(int CW, int cw, float scale_x, float off_x);
 hipError_t rcas_nv12_launch(const RcasArgs& a, const fsr1_rgb2ycbcr& yc, long long chroma_offset, int bits, int fin, bool exact, bool wide, hipStream_t stream);
 hipError_t easu_nv12_launch(const EasuArgs& a, const fsr1_ycbcr& ycbcr, long long chroma_offset, int bits, int fout, bool exact, bool s2, bool wide, hipStream_t stream);
 size_t easu_nv12_lds_bytes(int fp_w, int fp_h, int pair_bytes);
@@ -1237,6 +1240,112 @@ int fsr1_transcode_ycbcr(const fsr1_image* in, const fsr1_image* intermediary, c
   if (int rc = fsr1_easu_dispatch_ycbcr(in, intermediary, easu_con, ycbcr_in, math, stream)) return rc;  // :121
   FsrRcasCon(rcas_con, p->rcas_attenuation);                                                             // :124
   return fsr1_rcas_dispatch_ycbcr(intermediary, out, rcas_con, ycbcr_out, math | rcas_opts | out_policy | (p->hdr ? FSR1_FLAG_HDR_SQUARE : 0u), stream);  // :131
+}
+
+// ---- NV12 in, NV12 out in the luma domain (include/fsr1_hip.h, fsr1_rcas_luma.hip) ----
+// Two launches: the single-channel EASU of the Y plane into the uint8 intermediary (the existing dispatch, on a view), then one grid of
+// the single-channel RCAS strips (intermediary -> Y plane) followed by the chroma strips (CbCr plane -> CbCr plane).
+int fsr1_transcode_luma(const fsr1_image* in, const fsr1_image* intermediary, const fsr1_image* out, const fsr1_params* p, const fsr1_chroma420* chroma,
+                        void* stream) {
+  const Range range("transcode_luma", in, out);
+  if (!in || !out || !p || !chroma) return fail(FSR1_ERR_INVALID_ARGUMENT, "transcode_luma: null argument");
+  if (in->format != FSR1_FORMAT_NV12 || out->format != FSR1_FORMAT_NV12)
+    return fail(FSR1_ERR_UNSUPPORTED, "transcode_luma: input and output must both be FSR1_FORMAT_NV12 (P010 / P016 have no 16-bit single-channel kernels), got formats %d -> %d",
+                in->format, out->format);
+  if (int rc = check_flags(p->flags)) return rc;
+  const uint32_t math = p->flags & (FSR1_FLAG_MATH_EXACT | FSR1_FLAG_MATH_PACKED_FP16 | FSR1_FLAG_MATH_STRICT | FSR1_FLAG_NO_FAST_PATHS | FSR1_FLAG_FRAMES_OVERLAP);
+  const uint32_t rcas_opts = p->flags & FSR1_FLAG_RCAS_DENOISE;
+  const uint32_t out_policy = p->flags & (FSR1_FLAG_OUTPUT_STREAMING | FSR1_FLAG_OUTPUT_CACHED);  // of the launch that writes `out`
+  if (p->flags & ~(math | rcas_opts | out_policy))
+    return fail(FSR1_ERR_INVALID_ARGUMENT, "transcode_luma: params.flags may only hold MATH_*, RCAS_DENOISE, OUTPUT_* and FRAMES_OVERLAP bits");
+  if (p->flags & FSR1_FLAG_MATH_PACKED_FP16)
+    return fail(FSR1_ERR_UNSUPPORTED, "transcode_luma: the Y plane of an NV12 image runs with the F (binary32) arithmetic, not packed fp16");
+  if (p->hdr) return fail(FSR1_ERR_INVALID_ARGUMENT, "transcode_luma: hdr must be 0 (Y codes are not squared)");
+  if (!p->use_rcas)
+    return fail(FSR1_ERR_UNSUPPORTED, "transcode_luma: the NV12 Y plane is stored by RCAS's launch, which also resamples the chroma (use_rcas = 0)");
+  if (p->fused != 0 && p->fused != 1 && p->fused != 2) return fail(FSR1_ERR_INVALID_ARGUMENT, "transcode_luma: params.fused must be 0, 1 or 2 (auto)");
+  if (p->fused == 1 || !intermediary)
+    return fail(FSR1_ERR_UNSUPPORTED, "transcode_luma: NV12 images run as two launches; pass an intermediary and fused = 0 or 2");
+  if (intermediary->format != FSR1_FORMAT_R8_UNORM)
+    return fail(FSR1_ERR_UNSUPPORTED, "transcode_luma: between the NV12 images the intermediary must be FSR1_FORMAT_R8_UNORM, got format %d", intermediary->format);
+  for (const int s : {chroma->siting_in, chroma->siting_out})
+    if (s != FSR1_CHROMA_LEFT && s != FSR1_CHROMA_CENTER)
+      return fail(FSR1_ERR_UNSUPPORTED, "transcode_luma: %s NV12 chroma siting %d (the resampler takes LEFT and CENTER)", s == FSR1_CHROMA_REPLICATE ? "unsupported" : "unknown", s);
+  RcasArgs a;
+  ImageView vin;
+  a.xcd_shift = device_xcd_shift();
+  memset(&a.color, 0, sizeof a.color);
+  long long coff_in = 0, coff_out = 0, fbytes_in = 0, fbytes_out = 0;
+  if (int rc = check_nv12(in, chroma, "fsr1_chroma420", true, chroma->siting_in, chroma->chroma_offset_bytes_in, "transcode_luma input", "input", &vin, &coff_in, &fbytes_in))
+    return rc;
+  if (int rc = check_nv12(out, chroma, "fsr1_chroma420", true, chroma->siting_out, chroma->chroma_offset_bytes_out, "transcode_luma output", "output", &a.out, &coff_out,
+                          &fbytes_out))
+    return rc;
+  if (int rc = check_image(intermediary, "transcode_luma intermediary", &a.in)) return rc;
+  if (intermediary->width != out->width || intermediary->height != out->height || intermediary->frames != out->frames)
+    return fail(FSR1_ERR_INVALID_ARGUMENT, "transcode_luma: intermediary %dx%dx%d and output %dx%dx%d extents differ", intermediary->width, intermediary->height,
+                intermediary->frames, out->width, out->height, out->frames);
+  if (in->frames != out->frames) return fail(FSR1_ERR_INVALID_ARGUMENT, "transcode_luma: frame counts differ (%d vs %d)", in->frames, out->frames);
+  if (!(p->render_width >= 1.0f) || !(p->render_height >= 1.0f) || p->render_width > (float)in->width || p->render_height > (float)in->height)
+    return fail(FSR1_ERR_INVALID_ARGUMENT, "transcode_luma: render size %gx%g must lie within the input image %dx%d", (double)p->render_width,
+                (double)p->render_height, in->width, in->height);
+  {  // the overlap test of the other dispatches over all three images; an NV12 batch's last frame ends behind its chroma plane
+    const char* const b[3] = {vin.base, a.in.base, a.out.base};
+    const char* const e[3] = {vin.base + vin.frame_stride * (in->frames - 1) + fbytes_in,
+                              a.in.base + a.in.frame_stride * (intermediary->frames - 1) + a.in.pitch * intermediary->height,
+                              a.out.base + a.out.frame_stride * (out->frames - 1) + fbytes_out};
+    for (int i = 0; i < 3; ++i)
+      for (int j = i + 1; j < 3; ++j)
+        if (b[i] < e[j] && b[j] < e[i]) return fail(FSR1_ERR_INVALID_ARGUMENT, "transcode_luma: input, intermediary and output overlap");
+  }
+  // launch 2, prepared before anything runs: the RCAS strips exactly as fsr1_rcas_dispatch lays them out on these two single-channel views
+  const uint32_t rcas_flags = math | rcas_opts | out_policy;
+  uint32_t easu_con[16];
+  FsrEasuCon(easu_con, easu_con + 4, easu_con + 8, easu_con + 12, p->render_width, p->render_height, p->render_width, p->render_height,
+             (float)out->width, (float)out->height);  // FSR_Filter.cpp:106
+  FsrRcasCon(a.con, p->rcas_attenuation);             // :124
+  rcas_mono_geometry(FSR1_FORMAT_R8_UNORM, out->width, out->height, out->frames, (rcas_flags & FSR1_FLAG_FRAMES_OVERLAP) != 0, device_cus(), &a.tiles_x, &a.tiles_y,
+                     &a.rows);
+  a.frames = out->frames;
+  a.flags = resolve_output_policy(rcas_flags, true);
+  a.rows_above = a.rows_below = 0;
+  const long long access = (long long)rcas_mono_access_bytes(FSR1_FORMAT_R8_UNORM);
+  const bool wide = planar_aligned(intermediary, a.in, (size_t)access) && planar_aligned(out, a.out, (size_t)access);
+  const bool exact = (rcas_flags & (FSR1_FLAG_MATH_EXACT | FSR1_FLAG_MATH_STRICT)) != 0;
+  // the chroma grids' mapping, in double, each constant rounded to binary32 once (fsr1_hip.h)
+  Chroma420Args c;
+  const double sx = (double)p->render_width / (double)out->width, sy = (double)p->render_height / (double)out->height;
+  const double s_in = chroma->siting_in == FSR1_CHROMA_CENTER ? 0.5 : 0.0, s_out = chroma->siting_out == FSR1_CHROMA_CENTER ? 0.5 : 0.0;
+  c.scale_x = (float)sx;
+  c.scale_y = (float)sy;
+  c.off_x = (float)(((s_out + 0.5) * sx - 0.5 - s_in) / 2.0);
+  c.off_y = (float)(((0.5 + 0.5) * sy - 0.5 - 0.5) / 2.0);
+  c.in = vin.base + coff_in;
+  c.out = a.out.base + coff_out;
+  c.in_pitch = vin.pitch;
+  c.in_frame_stride = vin.frame_stride;
+  c.out_pitch = a.out.pitch;
+  c.out_frame_stride = a.out.frame_stride;
+  c.cw = (in->width + 1) / 2;
+  c.ch = (in->height + 1) / 2;
+  c.CW = (out->width + 1) / 2;
+  c.CH = (out->height + 1) / 2;
+  chroma420_geometry(c.CW, c.CH, &c.tiles_x, &c.tiles_y, &c.rows);
+  // wide forms only where every address they form is aligned to the access: input rows on dwords (and a lane's run within three of them),
+  // a lane's four output pairs on 8 bytes
+  auto aligned = [](const char* base, long long pitch, long long fstride, int frames, long long n) {
+    return !((uintptr_t)base % n) && !(pitch % n) && (frames == 1 || !(fstride % n));
+  };
+  c.in_wide = aligned(c.in, c.in_pitch, c.in_frame_stride, in->frames, 4) && chroma420_run_dwords(c.CW, c.cw, c.scale_x, c.off_x) <= 3;
+  c.out_wide = aligned(c.out, c.out_pitch, c.out_frame_stride, out->frames, 8);
+  if ((long long)a.tiles_x * a.tiles_y * a.frames + (long long)c.tiles_x * c.tiles_y * a.frames > 0x7fffffffLL)
+    return fail(FSR1_ERR_UNSUPPORTED, "transcode_luma: the RCAS and chroma strips exceed the launch grid limit; split the batch");
+  // launch 1: EASU of the Y plane, read as R8_UNORM, into the intermediary
+  const fsr1_image y_in = {in->data, in->width, in->height, FSR1_FORMAT_R8_UNORM, in->frames, vin.pitch, vin.frame_stride};
+  if (int rc = fsr1_easu_dispatch(&y_in, intermediary, easu_con, math, stream)) return rc;  // :121
+  // launch 2 (tools/experiments_luma/separate_launches.patch: rcas_mono and a chroma-only launch instead, for the measurement of 3.5g)
+  if (const hipError_t e = rcas_luma_launch(a, c, exact, wide, false, static_cast<hipStream_t>(stream)); e != hipSuccess) return hip_fail(e, "transcode_luma launch");  // :131
+  return FSR1_OK;
 }
 
 int fsr1_selftest(uint32_t* failures) {

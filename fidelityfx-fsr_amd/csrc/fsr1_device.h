@@ -53,6 +53,19 @@ struct RcasArgs {
   ColorArgs color;
 };
 
+// The CbCr planes of a 4:2:0 resample (fsr1_rcas_luma.hip): `in` / `out` point at the first pair of frame 0's pair plane, extents are in
+// pairs, and the four constants are the chroma grids' mapping of "THE PINNED LUMA-DOMAIN TRANSCODE" (fsr1_hip.h), rounded on the host.
+struct Chroma420Args {
+  const char* in;
+  char* out;
+  long long in_pitch, in_frame_stride, out_pitch, out_frame_stride;  // bytes; the Y plane's
+  int cw, ch, CW, CH;  // input pairs, output pairs
+  float scale_x, off_x, scale_y, off_y;
+  int tiles_x, tiles_y, rows;  // workgroups per strip row, strip rows, output pair rows per strip
+  int in_wide;   // every input row starts on a dword and a lane's run of pairs fits three of them: aligned dword loads
+  int out_wide;  // every lane's four pairs start on 8 bytes: one store
+};
+
 struct FusedArgs {
   ImageView in, out;
   int xcd_shift;  // log2 of the XCDs behind the device (3 on an MI355X in SPX mode): xcd_swizzle

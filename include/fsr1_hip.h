@@ -534,6 +534,47 @@ int fsr1_transcode_ycbcr(const fsr1_image* in, const fsr1_image* intermediary, c
                          const fsr1_ycbcr* ycbcr_in, const fsr1_rgb2ycbcr* ycbcr_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * NV12 in, NV12 out in the luma domain: EASU + RCAS on the Y plane alone, the CbCr plane through a bilinear resampler — the frame never
+ * becomes RGB, and neither the stream's matrix nor its range is needed.
+ *
+ * THE PINNED LUMA-DOMAIN TRANSCODE (the parity contract of fsr1_transcode_luma).
+ *   Luma.  The Y plane of `out` is what the single-channel chain stores: Y codes are read as FSR1_FORMAT_R8_UNORM, fsr1_easu_dispatch
+ *   runs into the intermediary with the constants fsr1_upscale derives from params (render size = viewport), fsr1_rcas_dispatch runs into
+ *   the Y plane — bit for bit what those two calls store on views of the same memory, in the default arithmetic and under
+ *   FSR1_FLAG_MATH_EXACT; FSR1_FLAG_MATH_STRICT takes EXACT, as for single-channel images.  Range is not interpreted (limited-range
+ *   codes are filtered as the UNORM values they are) and no colour matrix enters anywhere.
+ *   Chroma, for C = Cb and C = Cr alike.  Output pair (K, J), 0 <= K < CW = (ow + 1) / 2, 0 <= J < CH = (oh + 1) / 2; input pairs (k, j) in
+ *   [0, cw - 1] x [0, ch - 1]; rw x rh the render size.  The horizontal siting offset s is 0 for FSR1_CHROMA_LEFT and 0.5 for
+ *   FSR1_CHROMA_CENTER, the vertical one always 0.5.  The host computes, in double, rounding each of the four to binary32 once:
+ *     scale_x = rw / ow                                            scale_y = rh / oh
+ *     off_x   = ((s_out + 0.5) * (rw / ow) - 0.5 - s_in) / 2       off_y   = ((0.5 + 0.5) * (rh / oh) - 0.5 - 0.5) / 2
+ *   (EASU's own pixel-centre mapping, carried to the chroma grids).  On the device every product, sum and difference is rounded to
+ *   binary32 BY ITSELF, round-to-nearest-even, never contracted into a fused multiply-add, in every arithmetic mode:
+ *     u = (float)K * scale_x + off_x;   k0 = floor(u);   f = u - k0
+ *     a = C[clamp(k0)],  b = C[clamp(k0 + 1)]  as raw codes (indices clamped to [0, cw - 1])
+ *     h = a + f * (b - a)
+ *   on input rows clamp(j0) and clamp(j0 + 1), with j0 and g obtained from J, scale_y and off_y the same way (clamped to [0, ch - 1]):
+ *     v = h0 + g * (h1 - h0)
+ *     code = (uint8)(min(max(v, 0), 255) + 0.5f)        (NaN cannot occur)
+ *   Writes.  No byte outside the ow x oh Y bytes and the 2 CW x CH pair bytes of a frame is ever written.
+ * A binary32 restatement of the chroma lines (numpy float32) reproduces the pair plane byte for byte.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct fsr1_chroma420 {
+  int32_t siting_in, siting_out;        /* FSR1_CHROMA_LEFT or FSR1_CHROMA_CENTER, independently */
+  int64_t chroma_offset_bytes_in;       /* as fsr1_ycbcr.chroma_offset_bytes: 0 = pitch * height */
+  int64_t chroma_offset_bytes_out;
+} fsr1_chroma420;
+
+/* in, out: FSR1_FORMAT_NV12 (the NV12 surface rules above); intermediary: FSR1_FORMAT_R8_UNORM of out's extent and frame count.  Two
+ * launches: the single-channel EASU of the Y plane, then ONE grid that holds the single-channel RCAS strips and the chroma strips.
+ * params as for fsr1_upscale (MATH_EXACT / MATH_STRICT / NO_FAST_PATHS, RCAS_DENOISE, OUTPUT_*, FRAMES_OVERLAP in flags).
+ * FSR1_ERR_UNSUPPORTED ("NV12" in the message): P010 / P016 or any other format on either end, an intermediary that is not R8_UNORM or
+ * is missing, fused == 1, use_rcas == 0, FSR1_FLAG_MATH_PACKED_FP16, siting REPLICATE or unknown.  FSR1_ERR_INVALID_ARGUMENT: null
+ * pointers, hdr != 0, extents or frame counts that disagree, a render size outside the input, overlapping images, unknown flags. */
+int fsr1_transcode_luma(const fsr1_image* in, const fsr1_image* intermediary, const fsr1_image* out, const fsr1_params* params,
+                        const fsr1_chroma420* chroma, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Frame pipeline: independent frames on alternating HIP streams.
  *
  * FSR 1.0 keeps no history, so consecutive frames of a stream are independent — but dispatches on ONE HIP stream serialise,
